@@ -4,7 +4,13 @@
 HDK-semantics CPU path timed beside it.
 
     python bench.py --gpus N --steps K --warmup W [--config c2|c3|c5|c5s|q1..q4] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times K steps, writes the last step's result with --dump-outputs, and prints the line:
+`value` (rows/s), `ms_per_step`, and a roofline from the HIP events of the timed launches and the committed traffic profile.
+--full adds everything else described below: the result checks at full size and on an oracle sample, the live traffic
+passes, the measured HBM peak, the end-to-end leg, the CPU baseline, the other configs and the multi-GPU emulation.
 
 A step = one pass of the hot path over the rank's resident fragments: output-buffer init, the multi-fragment
 scan/aggregate launch (every pass of it), finalize and -- for N > 1 -- the partial-aggregate merge over RCCL/xGMI:
@@ -15,7 +21,7 @@ Inputs are resident in HBM before the timed region (as HDK keeps chunks cached i
 
 Scaling: STRONG by default -- ONE table of `--rows` rows in 32 M-row fragments, fragment f on rank
 f mod N, value = table rows / max-over-ranks step time.  `--scaling weak` gives every rank its own table.
-At N = 1 the line also carries, under "configs", the other BASELINE configurations at BASELINE size (C3 join probe,
+At N = 1 a --full line also carries, under "configs", the other BASELINE configurations at BASELINE size (C3 join probe,
 C5 open addressing and its per-GPU shard shape, taxi Q1-Q4), each with its own roofline object, and under
 "multi_gpu_emulated" the per-rank step of an 8-GPU job measured on this one device (wire excluded).
 """
@@ -294,10 +300,19 @@ def run_config(name, args, comm, mgr, steps, warmup, primary):
         scan_ms = [xch_ms["scatter"] + xch_ms["aggregate"]]  # this rank's kernels (its rows scattered, its keys aggregated)
     avg_scan_ms = float(np.mean(scan_ms)) if scan_ms else float("nan")
 
+    if primary and args.dump_outputs and rank == 0:  # (the last timed step's result, before any check runs another step)
+        if baseline:
+            table, n_e = (owner["table"], owner["entries"]) if multi else (out_t, cp.entry_count)
+        else:
+            table, n_e = (gathered[:quads] if multi else out_t), cp.entry_count
+        dump_outputs(args.dump_outputs, cp, table.cpu().numpy(), n_e)
+
     # ---- correctness at full size: size-independent properties (every rank takes part in the collectives) ----------
     checks = {}
-    ref = w.reference_checks()
-    if name in ("c2", "c5", "c5s"):
+    ref = w.reference_checks() if args.full else None
+    if not args.full:
+        pass  # (a plain run only times its steps)
+    elif name in ("c2", "c5", "c5s"):
         if baseline:
             tbl = owner["table"] if multi else out_t
             n_e = owner["entries"] if multi else cp.entry_count
@@ -399,7 +414,7 @@ def run_config(name, args, comm, mgr, steps, warmup, primary):
             checks["per_key_counts_equal_torch_bincount"] = bool([per.get(i, 0) for i in range(8)] == kc[:8])
 
     # ---- bit-exact parity with the oracle on a sample of the same data (rank 0) ------------------------------------
-    if rank == 0 and not args.no_oracle_sample:
+    if rank == 0 and args.full and not args.no_oracle_sample:
         from oracle import oracle as O
         from hdk_amd.executor import Executor
         from util import assert_buffers_equal, run_oracle
@@ -460,7 +475,7 @@ def run_config(name, args, comm, mgr, steps, warmup, primary):
                      "alg_bytes_per_row": w.alg_bytes_per_row,
                      "note": "per GPU: this rank's rows x algorithmic bytes / mean HIP-event time of the scan launch "
                              "(all of its passes)"},
-        "checks": checks,
+        "checks": checks if args.full else None,
         "setup_s": {"generate": t_gen},
     }
     if mode == "tables" and merge_ms:
@@ -476,6 +491,55 @@ def run_config(name, args, comm, mgr, steps, warmup, primary):
     step.free()
     w.resident_out = None if (multi or baseline) else out_t  # (the end-to-end run compares its buffer with this one)
     return out, w
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, cp, buf, entry_count):
+    """--dump-outputs: the rows a caller of the timed path receives (ExecutionResult.to_columns of the step's output buffer),
+    one float64 array per output column in DIR/<column>.npy -- NULL as NaN, a dictionary-encoded string as its code -- rows
+    sorted by every column, so that two builds compare output for output whatever their table layout.  Above DUMP_MAX_BYTES
+    in all, a fixed seeded sample of the sorted rows (an open-addressing table is thinned out by key before it is decoded).
+    With N > 1 ranks: rank 0's result (for open addressing, the groups rank 0 owns)."""
+    from hdk_amd import _abi as A
+    from hdk_amd import result_set as RS
+    from hdk_amd.executor import ExecutionResult
+    p = cp.plan
+    max_rows = max(DUMP_MAX_BYTES // (8 * max(len(cp.out_cols), 1)), 1)
+    if p.query_kind == A.Q_BASELINE_HASH:
+        live = np.flatnonzero(RS.non_empty_mask(cp, buf, entry_count))
+        if len(live) > max_rows:
+            keys = [k[live] for k in RS._key_arrays(cp, buf, entry_count)]
+            by_key = live[np.lexsort(keys[::-1])]
+            keep = by_key[np.sort(np.random.default_rng(DUMP_SEED).choice(len(by_key), max_rows, replace=False))]
+            drop = np.ones(entry_count, dtype=bool)
+            drop[keep] = False
+            buf = buf.copy()
+            raw = buf.view(np.uint8)
+            if p.output_columnar:  # key column 0 leads the buffer
+                raw[:entry_count * 8].view(np.int64)[drop] = A.EMPTY_KEY_64
+            else:
+                rows = raw[:entry_count * int(p.row_size_quad) * 8].reshape(entry_count, -1)
+                kw = int(p.key_width)
+                k0 = np.ascontiguousarray(rows[:, :kw]).view(np.int64 if kw == 8 else np.int32).reshape(-1)
+                k0[drop] = A.EMPTY_KEY_64 if kw == 8 else A.EMPTY_KEY_32
+                rows[:, :kw] = k0.view(np.uint8).reshape(entry_count, kw)
+    cols = ExecutionResult(cp, buf, entry_count).to_columns()
+    arrays = {}
+    for oc in cp.out_cols:
+        vals = cols[oc.name]
+        if oc.dictionary is not None:
+            code = {s: i for i, s in enumerate(oc.dictionary)}
+            vals = [None if v is None else code[v] for v in vals]
+        arrays[oc.name] = np.array([np.nan if v is None else v for v in vals], dtype=np.float64)
+    order = np.lexsort(list(arrays.values())[::-1]) if arrays else None
+    if order is not None and len(order) > max_rows:
+        order = order[np.sort(np.random.default_rng(DUMP_SEED).choice(len(order), max_rows, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, "".join(ch if ch.isalnum() or ch in "_-." else "_" for ch in name) + ".npy"), a[order])
 
 
 # The pass of a multi-kernel launch that takes the most time, by the rocprofv3 kernel statistics of this same command
@@ -928,13 +992,22 @@ def main():
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not measure roofline.traffic with rocprofv3 --pmc child passes (N = 1 default run); use the committed profile")
     ap.add_argument("--multi-gpu-emulation", choices=["c5", "full", "none"], default="c5",
-                    help="N = 1 default run: also measure one rank's step of an 8-GPU job on this device (c5: the tuple "
+                    help="N = 1 --full run: also measure one rank's step of an 8-GPU job on this device (c5: the tuple "
                          "exchange; full: plus C2's shard; none)")
     ap.add_argument("--no-multi-gpu-emulation", dest="multi_gpu_emulation", action="store_const", const="none")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, everything else the benchmark measures and checks: the result checks at "
+                         "full size and on an oracle sample, live traffic, measured HBM peak, end-to-end leg, CPU baseline, "
+                         "the other configs (--extra) and the multi-GPU emulation; without it a run only times its steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step to DIR/<column>.npy (float64, rows sorted; at most "
+                         "64 MB in all, a fixed seeded sample of the rows beyond that)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.extra not in ("auto", "none") and not args.full:
+        raise SystemExit("--extra runs other configs: it needs --full")
     if args.gpus > 1 and "RANK" not in os.environ:
         # No launcher: start the N ranks ourselves, as a CHILD process -- this parent has not touched HIP (nothing above
         # imports torch) and never replaces itself.  Rank 0's JSON line is the child's stdout, relayed as it comes.
@@ -943,8 +1016,8 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={os.environ['WORLD_SIZE']}: refusing to print a line for another job size")
 
     live = None
-    if (args.gpus == 1 and not args.no_live_traffic and "RANK" not in os.environ and args.extra == "auto" and args.config == "c2"
-            and not os.environ.get("HDK_BENCH_SINGLE_RANK_COLLECTIVES")):
+    if (args.full and args.gpus == 1 and not args.no_live_traffic and "RANK" not in os.environ and args.extra == "auto"
+            and args.config == "c2" and not os.environ.get("HDK_BENCH_SINGLE_RANK_COLLECTIVES")):
         live = measure_traffic_live(args.config, args.rows)  # (children: before this process touches the GPU)
 
     comm = Comm(args)
@@ -956,23 +1029,24 @@ def main():
         line["roofline"]["traffic"] = live["bytes_per_launch"]
         line["roofline"]["traffic_source"] = live["source"]
         line["roofline"]["traffic_kernels"] = live["kernels"]
-    if comm.rank == 0:
+    if comm.rank == 0 and args.full:
         copy_gbps, read_gbps = C.c_double(0), C.c_double(0)
         check(lib().hdk_hip_mgr_measure_hbm(comm.dev, 4 << 30, 3, C.byref(copy_gbps), C.byref(read_gbps)))
         line["roofline"]["peak_measured"] = {"read_GBps": read_gbps.value, "copy_GBps": copy_gbps.value,
                                              "what": "16 B/lane streaming read / copy (read + written bytes) of 4 GiB, best of 3"}
         if line["roofline"]["achieved"]:
             line["roofline"]["frac_of_measured_read"] = line["roofline"]["achieved"] / read_gbps.value
-    if comm.rank == 0 and comm.world == 1 and not args.no_end_to_end and args.config == "c2" and w.resident_out is not None:
+    if args.full and comm.rank == 0 and comm.world == 1 and not args.no_end_to_end and args.config == "c2" and w.resident_out is not None:
         line["end_to_end"] = end_to_end(w, mgr, comm, w.resident_out)
-    if comm.rank == 0 and comm.world == 1 and not args.no_cpu_baseline and args.config == "c2":
+    if args.full and comm.rank == 0 and comm.world == 1 and not args.no_cpu_baseline and args.config == "c2":
         line["cpu_baseline"] = cpu_baseline(w, args)
     else:
         line["cpu_baseline"] = None
     del w
     extra = args.extra
     if extra == "auto":
-        extra = "c3,c3g,c3gm,c3m,bh1,bh3,bh4,bh5,nga2,msbs1,msphs1,msphs1w,msphs1f,phm2,c5,c5s,q1,q2,q3,q4" if (comm.world == 1 and args.config == "c2" and not args.rows) else ""
+        extra = "c3,c3g,c3gm,c3m,bh1,bh3,bh4,bh5,nga2,msbs1,msphs1,msphs1w,msphs1f,phm2,c5,c5s,q1,q2,q3,q4" if (
+            args.full and comm.world == 1 and args.config == "c2" and not args.rows) else ""
     if extra == "none":
         extra = ""
     configs = []
@@ -987,7 +1061,7 @@ def main():
         configs.append({k: o[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "config", "roofline", "checks")})
     if configs:
         line["configs"] = configs
-    if comm.rank == 0 and comm.world == 1 and args.config == "c2" and not args.rows and args.multi_gpu_emulation != "none":
+    if args.full and comm.rank == 0 and comm.world == 1 and args.config == "c2" and not args.rows and args.multi_gpu_emulation != "none":
         # What one rank of an 8-GPU job does per step, measured here on one device (everything but the wire):
         # C2's shard (4 of 32 fragments) incl. init, finalize, an emulated all-gather and the fold of 7 partials; C5's
         # tuple exchange, all 8 ranks and owners one after another (scripts/multi_gpu_floor.py)

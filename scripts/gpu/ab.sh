@@ -3,7 +3,7 @@
 # runs bench.py for each config with the default library and with hdk_amd/libhdk_hip_<variant>.so, alternating, twice.
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 V=$1; shift
-Q="--steps 10 --warmup 3 --no-cpu-baseline --no-oracle-sample --no-multi-gpu-emulation --extra none"
+Q="--steps 10 --warmup 3 --full --no-cpu-baseline --no-oracle-sample --no-multi-gpu-emulation --extra none"
 for rep in 1 2; do
   for c in "$@"; do
     for lib in default $V; do

@@ -6,7 +6,7 @@
 //                                           JoinColumn, JoinColumnTypeInfo  (the header includes Logger.h -> Boost)
 //   ResultSet/ResultType.h:28-34            QueryDescriptionType
 // Same names, members, member order and signatures; nothing else.  DataMgr/GpuMgr.h is NOT restated anywhere: the
-// harness is built against the reference's own header (tests/cpp/Makefile).
+// harness is built against the reference's own header (oracle/Makefile, target `cpp`).
 #pragma once
 
 #include <cstddef>

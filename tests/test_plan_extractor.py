@@ -17,7 +17,7 @@ from hdk_amd.plan import compile_query
 from hdk_amd.storage import ArrowStorage
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "tests", "cpp", "_build", "extract_dump")
+EXE = os.path.join(ROOT, "oracle", "_ref", "cpp", "extract_dump")
 
 
 def _tables():
@@ -117,10 +117,8 @@ def _expr_half(p):
 
 @pytest.fixture(scope="module")
 def dumped(tmp_path_factory):
-    if os.path.isdir("/root/reference/omniscidb"):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "--no-print-directory"], stdout=subprocess.DEVNULL)
     if not os.path.exists(EXE):
-        pytest.skip("tests/cpp/_build/extract_dump is missing (built where the reference tree exists)")
+        pytest.skip("oracle/_ref/cpp/extract_dump is missing (built where the reference tree exists)")
     d = tmp_path_factory.mktemp("plans")
     r = subprocess.run([EXE, str(d)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
