@@ -12,6 +12,7 @@
 #include "../../include/hdk_hip.h"
 
 #define HDK_DEV __device__ __forceinline__
+#define HDK_HOST_DEV __host__ __device__ __forceinline__  // layout arithmetic the host needs too
 
 namespace hdk {
 
@@ -754,9 +755,9 @@ HDK_DEV int32_t float_slot_null(const hdk_hip_target& tg) {
 // ---------------------------------------------------------------------------------------------
 // columnar layout helpers (RS/QueryMemoryDescriptor.cpp getColOffInBytes)
 // ---------------------------------------------------------------------------------------------
-HDK_DEV size_t align8(size_t x) { return (x + 7) & ~static_cast<size_t>(7); }
+HDK_HOST_DEV size_t align8(size_t x) { return (x + 7) & ~static_cast<size_t>(7); }
 
-HDK_DEV size_t columnar_slot_off(const hdk_hip_plan* p, uint32_t entry_count, int slot) {
+HDK_HOST_DEV size_t columnar_slot_off(const hdk_hip_plan* p, uint32_t entry_count, int slot) {
   size_t off = p->keyless ? 0 : static_cast<size_t>(p->key_count) * align8(static_cast<size_t>(entry_count) * 8);
   if (p->query_kind == HDK_Q_PROJECTION) {
     off = align8(static_cast<size_t>(entry_count) * 8);  // the row-position column

@@ -15,6 +15,7 @@
 
 #include "baseline_table.h"
 #include "device_common.h"
+#include "group_buffer.h"
 #include "host_common.h"
 
 namespace hdk {
@@ -62,12 +63,6 @@ static int32_t cached_device_plan(const hdk_hip_plan* plan, int32_t device_id, c
 }
 
 constexpr int kRedBlock = 256;
-constexpr int kMaxSlots = 2 * HDK_HIP_MAX_TARGETS;
-
-struct SlotInit {
-  int64_t v[kMaxSlots];
-};
-
 // reduceOneSlotSingleValue (QE/ResultSetReduction.cpp:1186-1230): by slot width, against the slot's init value; true =
 // two different values ("Multiple distinct values encountered")
 HDK_DEV bool reduce_single_value(const hdk_hip_target& tg, int8_t* this1, const int8_t* that1, int64_t init_val) {
@@ -201,76 +196,6 @@ HDK_DEV void reduce_slot(const hdk_hip_target& tg, int8_t* this1, int8_t* this2,
   } else {
     *s = static_cast<int64_t>(static_cast<uint64_t>(old) + static_cast<uint64_t>(o));
   }
-}
-
-HDK_DEV int64_t read_slot(const int8_t* p, int w) {
-  return w == 4 ? static_cast<int64_t>(*reinterpret_cast<const int32_t*>(p)) : *reinterpret_cast<const int64_t*>(p);
-}
-
-HDK_DEV void slot_ptrs(const hdk_hip_plan* p, int64_t* buf, uint32_t entry_count, uint32_t entry, int t,
-                       int first_slot, int8_t** s1, int8_t** s2) {
-  const hdk_hip_target& tg = p->targets[t];
-  if (p->query_kind == HDK_Q_NON_GROUPED) {
-    *s1 = reinterpret_cast<int8_t*>(buf + first_slot);
-    *s2 = reinterpret_cast<int8_t*>(buf + first_slot + 1);
-  } else if (p->output_columnar) {
-    *s1 = reinterpret_cast<int8_t*>(buf) + columnar_slot_off(p, entry_count, first_slot) +
-          static_cast<size_t>(entry) * tg.slot_width;
-    *s2 = tg.agg == HDK_AGG_AVG ? reinterpret_cast<int8_t*>(buf) + columnar_slot_off(p, entry_count, first_slot + 1) +
-                                      static_cast<size_t>(entry) * tg.slot2_width
-                                : nullptr;
-  } else {
-    int8_t* row = reinterpret_cast<int8_t*>(buf + static_cast<size_t>(entry) * p->row_size_quad);
-    *s1 = row + tg.slot_off;
-    *s2 = row + tg.slot2_off;
-  }
-}
-
-// ResultSetStorage::isEmptyEntry[Columnar] (RS/ResultSetStorage.cpp:439-521)
-HDK_DEV bool is_empty_entry(const hdk_hip_plan* p, const int64_t* buf, uint32_t entry_count, uint32_t e,
-                            const SlotInit& init) {
-  if (p->query_kind == HDK_Q_NON_GROUPED) {
-    return false;
-  }
-  if (p->keyless) {
-    const int ks = p->idx_target_as_key;
-    int s = 0;
-    const int nt = p->num_targets;
-    for (int t = 0; t < nt; ++t) {
-      const hdk_hip_target& tg = p->targets[t];
-      const int n = tg.agg == HDK_AGG_AVG ? 2 : 1;
-      if (ks < s + n) {
-        int8_t *s1, *s2;
-        slot_ptrs(p, const_cast<int64_t*>(buf), entry_count, e, t, s, &s1, &s2);
-        const bool second = ks != s;
-        const int w = second ? tg.slot2_width : tg.slot_width;
-        int64_t iv = init.v[0];
-#pragma unroll
-        for (int k = 1; k < kMaxSlots; ++k) {
-          if (k == ks) iv = init.v[k];
-        }
-        if (w == 4) iv = static_cast<int32_t>(iv);
-        return read_slot(second ? s2 : s1, w) == iv;
-      }
-      s += n;
-    }
-    return true;
-  }
-  if (p->output_columnar) {
-    return buf[e] == HDK_EMPTY_KEY_64;
-  }
-  const int64_t* keys = buf + static_cast<size_t>(e) * p->row_size_quad;
-  return p->key_width == 4 ? *reinterpret_cast<const int32_t*>(keys) == HDK_EMPTY_KEY_32
-                           : *keys == HDK_EMPTY_KEY_64;
-}
-
-HDK_DEV int64_t slot_init(const SlotInit& init, int idx) {
-  int64_t iv = init.v[0];
-#pragma unroll
-  for (int k = 1; k < kMaxSlots; ++k) {
-    if (k == idx) iv = init.v[k];
-  }
-  return iv;
 }
 
 constexpr int kMaxThat = 16;
@@ -549,16 +474,6 @@ static size_t table_quads(const hdk_hip_plan* p, uint32_t entry_count) {
     }
   }
   return ((off + 7) & ~size_t(7)) / 8;
-}
-
-static void fill_slot_init(const hdk_hip_plan* plan, const int64_t* init_vals, SlotInit* init) {
-  int nslots = 0;
-  for (int t = 0; t < plan->num_targets; ++t) {
-    nslots += plan->targets[t].agg == HDK_AGG_AVG ? 2 : 1;
-  }
-  for (int i = 0; i < kMaxSlots; ++i) {
-    init->v[i] = i < nslots ? init_vals[i] : 0;
-  }
 }
 
 template <int MODE>

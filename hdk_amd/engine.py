@@ -41,11 +41,13 @@ class Engine:
         return self._executor
 
     def execute(self, q: QueryUnit, device_type: str = "GPU", **kw):
-        """-> ExecutionResult (buffer in the reference's layout, error code, to_arrow())."""
+        """-> ExecutionResult (buffer in the reference's layout, error code, to_arrow()); with result="columns" a
+        DeviceColumns instead (dense columns that stay in device memory, Executor.execute)."""
         if device_type.upper() != "GPU":
             raise QueryMustRunOnCpu("this package ships the GPU path only")
         return self.executor().execute(q, **kw)
 
     def run(self, q: QueryUnit, device_type: str = "GPU", **kw):
-        """-> pyarrow.Table with the targets' names and types, rows in buffer order."""
+        """-> pyarrow.Table with the targets' names and types, rows in buffer order (result="columns": the same table,
+        made from device-side columns instead of a host copy of the buffer)."""
         return self.execute(q, device_type, **kw).to_arrow()

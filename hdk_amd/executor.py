@@ -88,6 +88,59 @@ class ExecutionResult:
         return int(result_set.non_empty_mask(self.compiled, self.buffer, self.entry_count).sum())
 
 
+class DeviceColumns:
+    """Dense result columns in device memory: what hdk_hip_columnarize_result made of a group-by buffer (the device form
+    of the reference's ColumnarResults for a ResultSet that lives in HBM).  One 8-byte column per target, rows in entry
+    order -- the order ExecutionResult.to_columns() gives.  Owns its device block until free()."""
+
+    def __init__(self, cp: CompiledPlan, mgr: HipMgr, device_id: int, block: Optional[DeviceBuffer], capacity: int,
+                 num_rows: int, error_code: int = 0):
+        self.compiled, self.mgr, self.device_id = cp, mgr, device_id
+        self.block, self.capacity, self.num_rows, self.error_code = block, int(capacity), int(num_rows), error_code
+
+    def device_ptr(self, target_idx: int) -> int:
+        """Device address of target `target_idx`'s column: num_rows 8-byte values."""
+        if not 0 <= target_idx < self.compiled.plan.num_targets:
+            raise IndexError(target_idx)
+        if self.block is None or not self.block.ptr:
+            raise ValueError("the columns have been freed")
+        return self.block.ptr + target_idx * self.capacity * 8
+
+    def _is_fp(self, target_idx: int) -> bool:
+        tg = self.compiled.plan.targets[target_idx]
+        if tg.agg == A.AGG_ID:
+            return bool(self.compiled.key_types[tg.key_idx].is_fp)
+        return tg.agg == A.AGG_AVG or (bool(tg.arg_is_fp) and tg.agg != A.AGG_COUNT)
+
+    def to_host(self) -> List[np.ndarray]:
+        """One numpy array of num_rows values per target: float64 for fp values (AVG, fp aggregates, fp keys), int64
+        for everything else.  NULLs stay in band (the slot's sentinel sign-extended; NULL_DOUBLE for fp values)."""
+        nt = self.compiled.plan.num_targets
+        n = self.num_rows
+        if n == 0:
+            return [np.empty(0, dtype=np.float64 if self._is_fp(t) else np.int64) for t in range(nt)]
+        if self.capacity == n:  # exactly sized: one copy
+            flat = self.mgr.to_host(self.device_ptr(0), nt * n * 8, self.device_id, np.int64)
+            cols = [flat[t * n:(t + 1) * n] for t in range(nt)]
+        else:
+            cols = [self.mgr.to_host(self.device_ptr(t), n * 8, self.device_id, np.int64) for t in range(nt)]
+        return [c.view(np.float64) if self._is_fp(t) else c for t, c in enumerate(cols)]
+
+    def to_columns(self):
+        return result_set.dense_to_columns(self.compiled, [c.view(np.int64) for c in self.to_host()])
+
+    def to_arrow(self):
+        return result_set.columns_to_arrow(self.compiled, self.to_columns())
+
+    def row_count(self):
+        return self.num_rows
+
+    def free(self):
+        if self.block is not None:
+            self.block.free()
+            self.block = None
+
+
 class PreparedStep:
     """Everything one (multi-fragment) kernel launch needs, resident on the device."""
 
@@ -341,6 +394,53 @@ class PreparedStep:
         # QueryExecutionContext.cpp:221-234, surfaces it only when nothing positive happened)
         return ExecutionResult(self.cp, buf[:self.buffer_bytes // 8], self.cp.entry_count, err, total)
 
+    # below this many bytes of worst-case output (num_targets x entry_count x 8) the columns are made in ONE call into
+    # a block of `entry_count` rows; above it the groups are counted first and the block is sized exactly
+    COLUMNS_ONE_CALL_BYTES = 64 << 20
+
+    def fetch_columns(self, stream_synced=False) -> DeviceColumns:
+        """The step's result as dense device columns (hdk_hip_columnarize_result): the buffer stays in HBM, only what
+        to_host() asks for crosses the link.  Group-by steps only (the library rejects projections and non-grouped
+        aggregates: HDK_HIP_ERR_UNSUPPORTED).  The device error code is checked as in fetch().
+        Sizing: when num_targets x entry_count x 8 is at most COLUMNS_ONE_CALL_BYTES (64 MiB) one call writes into a block
+        of entry_count rows per column -- over-allocating a few MB costs less than a second pass over the table.  Above
+        that the groups are counted first (out_cols = NULL: one streaming pass) and the block holds exactly row_count
+        rows per column: a half-empty 200 M-entry table then takes 1.6 GB, not 3.2 GB."""
+        if not stream_synced:
+            self.mgr.synchronizeStream(self.dev)
+        err = int(self.mgr.to_host(self.d_err.ptr, 4, self.dev, np.int32)[0])
+        if err > 0:
+            raise HdkHipError(err, f"device error code {err} (QE/Execute.h:1019-1031)")
+        p = self.cp.plan
+        n, nt = int(self.cp.entry_count), int(p.num_targets)
+        iv = np.ascontiguousarray(self.cp.init_vals, dtype=np.int64)
+        d_rows = self.mgr.alloc(8, self.dev)
+        block = None
+
+        def call(out_ptr, capacity):
+            check(self.L.hdk_hip_columnarize_result(C.byref(p), self.out_ptr, n, iv.ctypes.data, out_ptr, capacity,
+                                                    d_rows.ptr, None, 0, self.dev, None))
+            self.mgr.synchronizeStream(self.dev)
+            return int(self.mgr.to_host(d_rows.ptr, 8, self.dev, np.uint64)[0])
+
+        try:
+            if nt * n * 8 <= self.COLUMNS_ONE_CALL_BYTES:
+                block = self.mgr.alloc(max(nt * n * 8, 8), self.dev)
+                capacity = n
+                rows = call(block.ptr, capacity)
+            else:
+                rows = capacity = call(None, 0)
+                if rows:
+                    block = self.mgr.alloc(nt * rows * 8, self.dev)
+                    call(block.ptr, capacity)
+        except Exception:
+            if block is not None:
+                block.free()
+            raise
+        finally:
+            d_rows.free()
+        return DeviceColumns(self.cp, self.mgr, self.dev, block, capacity, rows, err)
+
     def run(self, stream=None) -> ExecutionResult:
         self.enqueue(stream)
         return self.fetch()
@@ -522,9 +622,13 @@ class Executor:
             frag_ids = list(range(outer.num_fragments))
         return PreparedStep(self, cp, frag_ids, grid=grid, flags=flags, out_ptr=out_ptr, watchdog_ms=watchdog_ms)
 
-    def execute(self, q: QueryUnit, device_type: str = "GPU", frag_ids=None, **kw) -> ExecutionResult:
+    def execute(self, q: QueryUnit, device_type: str = "GPU", frag_ids=None, result: str = "buffer", **kw):
+        """-> ExecutionResult (the host copy of the buffer), or with result="columns" a DeviceColumns: the step's dense
+        columns in device memory (group-by steps; PreparedStep.fetch_columns)."""
         if device_type != "GPU":
             raise QueryMustRunOnCpu("hdk_amd ships the GPU path only; run device_type='CPU' on HDK itself")
+        if result not in ("buffer", "columns"):
+            raise ValueError(f"result must be 'buffer' or 'columns', not {result!r}")
         # A QueryUnit whose open-addressing table the PLANNER sized (no baseline_entry_count): running out of slots means
         # the estimate was wrong (stale statistics, a key from an inner column) -- RelAlgExecutor::handleOutOfMemoryRetry
         # (QE/RelAlgExecutor.cpp:1713-1747) re-runs with a doubled max_groups_buffer_entry_guess, at most twice more, and
@@ -534,6 +638,9 @@ class Executor:
         while True:
             step = self.prepare(q, frag_ids, **kw)
             try:
+                if result == "columns":
+                    step.enqueue()
+                    return step.fetch_columns()
                 return step.run()
             except HdkHipError as e:
                 if e.code != A.ERR_OUT_OF_SLOTS or step.cp.plan.query_kind != A.Q_BASELINE_HASH or retries_left == 0:

@@ -168,4 +168,22 @@ inline void fill_one_to_many_baseline_hash_table_on_device(int32_t* buff, const 
                                                      key_component_count, W, cols, tis, device_id, nullptr));
 }
 
+// ColumnarResults for a ResultSet whose storage is on the device: what the ColumnarResults constructor
+// (ResultSetRegistry/ColumnarResults.cpp:66-123) would call in place of materializeAllColumnsGroupBy (:691-1010) when
+// rows.getDeviceType() is GPU.  `plan` describes the buffer's layout (HipPlanBuilder.h, from the QueryMemoryDescriptor),
+// `init_vals` is ResultSetStorage::target_init_vals_ (a host vector), `entry_count` that of the buffer handed in.
+// Column t of the result starts at out_cols + t * capacity; *row_count_dev (device memory) receives the number of
+// non-empty entries, also when out_cols is null (count only) or the capacity is smaller.  `workspace` comes from the
+// BufferProvider (columnar_results_workspace_bytes(entry_count) bytes) or is null (the stream's memory pool).
+inline size_t columnar_results_workspace_bytes(const uint32_t entry_count) {
+  return hdk_hip_result_columns_workspace_bytes(entry_count);
+}
+inline void columnarize_result_on_device(const hdk_hip_plan& plan, const int64_t* groups_buffer, const uint32_t entry_count,
+                                         const int64_t* init_vals, int64_t* out_cols, const size_t capacity,
+                                         uint64_t* row_count_dev, int8_t* workspace, const size_t workspace_bytes,
+                                         const int device_id) {
+  check(hdk_hip_columnarize_result(&plan, groups_buffer, entry_count, init_vals, out_cols, static_cast<uint64_t>(capacity),
+                                   row_count_dev, workspace, workspace_bytes, device_id, nullptr));
+}
+
 }  // namespace hip_rt

@@ -151,82 +151,115 @@ def to_columns(cp: CompiledPlan, buf: np.ndarray, entry_count=None, nrows=None) 
     for oc in cp.out_cols:
         tg = p.targets[oc.target_idx]
         fs = first_slot[oc.target_idx]
-        w = cp.slot_widths[fs]
         # a projected key without a slot of its own comes from the key columns (target_groupby_indices)
         vals = (slots[fs] if slots[fs] is not None else keys[oc.key_idx])[mask]
-        if oc.kind == "key":
-            kt = cp.key_types[oc.key_idx]
-            nullv = kt.null_value()
-            col = []
-            if kt.is_fp:  # the key word holds the double's bits (groupByColumnCodegen's bit-cast, QE/IRCodegen.cpp:1219-1221)
-                fv = np.ascontiguousarray(vals, dtype=np.int64).view(np.float64)
-                # (a FLOAT key sits in the word widened to double, its NULL the widened FLOAT sentinel: makeTargetValue's case 8)
-                null_bits = kt.null_as_int64_or_double_bits()
-                if kt.size == 4:
-                    fv = fv.astype(np.float32).astype(np.float64)
-                for v, f in zip(vals.tolist(), fv.tolist()):
-                    col.append(None if (kt.nullable and v == null_bits) else f)
-                res[oc.name] = col
-                continue
-            for v in vals.tolist():
-                if kt.nullable and v == nullv:
-                    col.append(None)
-                elif oc.dictionary is not None:
-                    col.append(oc.dictionary[v])
-                else:
-                    col.append(v)
-            res[oc.name] = col
-            continue
-        if oc.agg == "count":
-            res[oc.name] = [int(v) for v in vals.tolist()]
-            continue
-        nullv = int(tg.null_val)
-        if w == 4:
-            nullv = int(np.int64(nullv).astype(np.int32))
-        nullable = bool(tg.skip_null)
-        float_slot = tg.arg_is_fp == A.FP_SLOT_FLOAT
-        if float_slot:
-            # takes_float_argument: the value is the float in the slot's low 4 bytes (ResultSetIteration.cpp:50-60,
-            # actual_compact_sz = sizeof(float)); NULL when those bits are the float sentinel
-            vals = (vals.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
-            fvals = vals.view(np.float32).astype(np.float64)
-            is_null = vals == np.uint32(A.NULL_FLOAT_BITS)
-        if oc.agg == "avg":
-            cnt = slots[fs + 1][mask]
-            col = []
-            for i, (sv, c) in enumerate(zip(vals.tolist(), cnt.tolist())):
-                if c == 0:
-                    col.append(None)  # load_avg_*: null when count == 0
-                elif float_slot:
-                    col.append(float(fvals[i]) / c)
-                elif tg.arg_is_fp:
-                    col.append(float(np.int64(sv).view(np.float64)) / c)
-                else:
-                    col.append(sv / c)
-            # decimal arguments: AVG(decimal) is scaled back (ResultSetIteration.cpp pair_to_double)
-            if oc.scale:
-                col = [None if v is None else v / 10 ** oc.scale for v in col]
-            res[oc.name] = col
-            continue
-        col = []
-        for i, v in enumerate(vals.tolist()):
-            if float_slot:
-                col.append(None if (nullable and is_null[i]) else float(fvals[i]))
-            elif nullable and v == nullv:
-                col.append(None)
-            elif tg.arg_is_fp:
-                col.append(float(np.int64(v).view(np.float64)))
-            else:
-                col.append(v)
-        if oc.scale and oc.agg in ("sum", "min", "max"):
-            col = [None if v is None else v / 10 ** oc.scale for v in col]
-        res[oc.name] = col
+        cnt = slots[fs + 1][mask] if oc.agg == "avg" else None
+        res[oc.name] = _column_values(cp, oc, vals, cnt, cp.slot_widths[fs])
     return res
 
 
+def _column_values(cp: CompiledPlan, oc, vals: np.ndarray, cnt, w: int, dense: bool = False) -> list:
+    """One output column as a python list (None = NULL) from the values of its non-empty entries, in entry order.
+    dense=False: `vals` are the slot (or key) words sign-extended to int64 and `cnt` AVG's count slot -- what the host
+    reader takes out of a buffer.  dense=True: `vals` are the 8-byte values of a device column
+    (hdk_hip_columnarize_result): a float accumulator is already widened to double bits (NULL_FLOAT -> NULL_DOUBLE for a
+    nullable argument) and AVG is already divided (NULL_DOUBLE for count 0); `cnt` is None.  `w`: the slot's width in the buffer."""
+    p = cp.plan
+    tg = p.targets[oc.target_idx]
+    if oc.kind == "key":
+        kt = cp.key_types[oc.key_idx]
+        nullv = kt.null_value()
+        col = []
+        if kt.is_fp:  # the key word holds the double's bits (groupByColumnCodegen's bit-cast, QE/IRCodegen.cpp:1219-1221)
+            fv = np.ascontiguousarray(vals, dtype=np.int64).view(np.float64)
+            # (a FLOAT key sits in the word widened to double, its NULL the widened FLOAT sentinel: makeTargetValue's case 8)
+            null_bits = kt.null_as_int64_or_double_bits()
+            if kt.size == 4:
+                fv = fv.astype(np.float32).astype(np.float64)
+            for v, f in zip(vals.tolist(), fv.tolist()):
+                col.append(None if (kt.nullable and v == null_bits) else f)
+            return col
+        for v in vals.tolist():
+            if kt.nullable and v == nullv:
+                col.append(None)
+            elif oc.dictionary is not None:
+                col.append(oc.dictionary[v])
+            else:
+                col.append(v)
+        return col
+    if oc.agg == "count":
+        return [int(v) for v in vals.tolist()]
+    nullv = int(tg.null_val)
+    if w == 4:
+        nullv = int(np.int64(nullv).astype(np.int32))
+    nullable = bool(tg.skip_null)
+    float_slot = tg.arg_is_fp == A.FP_SLOT_FLOAT
+    if dense and (float_slot or oc.agg == "avg"):
+        # the device has done the widening / the division; its NULL is NULL_DOUBLE (a nullable float accumulator, AVG's
+        # count 0).  (An AVG that comes out as exactly DBL_MIN would read as NULL here: sums of that size do not occur.)
+        bits = np.ascontiguousarray(vals, dtype=np.int64)
+        can_be_null = oc.agg == "avg" or nullable
+        col = [None if (can_be_null and b == A.NULL_DOUBLE_BITS) else f
+               for b, f in zip(bits.tolist(), bits.view(np.float64).tolist())]
+        if oc.scale and oc.agg in ("sum", "min", "max", "avg"):
+            col = [None if v is None else v / 10 ** oc.scale for v in col]
+        return col
+    if float_slot:
+        # takes_float_argument: the value is the float in the slot's low 4 bytes (ResultSetIteration.cpp:50-60,
+        # actual_compact_sz = sizeof(float)); NULL when those bits are the float sentinel
+        vals = (vals.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+        fvals = vals.view(np.float32).astype(np.float64)
+        is_null = vals == np.uint32(A.NULL_FLOAT_BITS)
+    if oc.agg == "avg":
+        col = []
+        for i, (sv, c) in enumerate(zip(vals.tolist(), cnt.tolist())):
+            if c == 0:
+                col.append(None)  # load_avg_*: null when count == 0
+            elif float_slot:
+                col.append(float(fvals[i]) / c)
+            elif tg.arg_is_fp:
+                col.append(float(np.int64(sv).view(np.float64)) / c)
+            else:
+                col.append(sv / c)
+        # decimal arguments: AVG(decimal) is scaled back (ResultSetIteration.cpp pair_to_double)
+        if oc.scale:
+            col = [None if v is None else v / 10 ** oc.scale for v in col]
+        return col
+    col = []
+    for i, v in enumerate(vals.tolist()):
+        if float_slot:
+            col.append(None if (nullable and is_null[i]) else float(fvals[i]))
+        elif nullable and v == nullv:
+            col.append(None)
+        elif tg.arg_is_fp:
+            col.append(float(np.int64(v).view(np.float64)))
+        else:
+            col.append(v)
+    if oc.scale and oc.agg in ("sum", "min", "max"):
+        col = [None if v is None else v / 10 ** oc.scale for v in col]
+    return col
+
+
+def dense_to_columns(cp: CompiledPlan, dense: List[np.ndarray]) -> Dict[str, list]:
+    """to_columns() from dense device columns: dense[t] holds target t's 8-byte values (int64 words), one per group in
+    entry order, as hdk_hip_columnarize_result writes them.  The same names, order, NULLs, dictionary strings and
+    decimal scaling as to_columns() on the buffer the columns were made from."""
+    first_slot, s = [], 0
+    for ti in range(cp.plan.num_targets):
+        first_slot.append(s)
+        s += 2 if cp.plan.targets[ti].agg == A.AGG_AVG else 1
+    return {oc.name: _column_values(cp, oc, np.ascontiguousarray(dense[oc.target_idx]).view(np.int64), None,
+                                    cp.slot_widths[first_slot[oc.target_idx]], dense=True)
+            for oc in cp.out_cols}
+
+
 def to_arrow(cp: CompiledPlan, buf: np.ndarray, entry_count=None, nrows=None):
+    return columns_to_arrow(cp, to_columns(cp, buf, entry_count, nrows))
+
+
+def columns_to_arrow(cp: CompiledPlan, cols: Dict[str, list]):
+    """{column name: python list} (to_columns / dense_to_columns) -> pyarrow.Table with the targets' names and types."""
     import pyarrow as pa
-    cols = to_columns(cp, buf, entry_count, nrows)
     arrays, names = [], []
     for oc in cp.out_cols:
         v = cols[oc.name]

@@ -567,6 +567,39 @@ int32_t hdk_hip_partition_baseline(const hdk_hip_plan* plan, const int64_t* buf,
                                    int64_t* const* seg_bufs, int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Columnar results on the device.
+ * Replaces, for a ResultSet whose storage sits in HBM, ColumnarResults::materializeAllColumnsGroupBy with its two stages
+ * locateAndCountEntries / compactAndCopyEntries (omniscidb/ResultSetRegistry/ColumnarResults.cpp:691-1010), which the
+ * reference runs on the host after copying the whole buffer, empty entries included.  A group-by buffer in the plan's
+ * layout (HDK_Q_PERFECT_HASH or HDK_Q_BASELINE_HASH: row-wise or columnar, keyless, 4- or 8-byte keys and slots,
+ * zero-width slots of projected baseline keys; any other query kind is HDK_HIP_ERR_UNSUPPORTED) becomes one dense 8-byte
+ * column per target: column t starts at out_cols + t * capacity, and row r of every column is the r-th non-empty entry
+ * in ascending entry index -- ResultSet iteration order.  An entry is empty as ResultSetStorage::isEmptyEntry[Columnar]
+ * says (omniscidb/ResultSet/ResultSetStorage.cpp:439-521).  A value is what iteration returns for the target:
+ *   HDK_AGG_ID                      the slot, sign-extended; with slot_width == 0 key column key_idx (a 4-byte key
+ *                                   sign-extended, an fp key's bit pattern unchanged)
+ *   COUNT, integer SUM / MIN / MAX / SINGLE_VALUE
+ *                                   the slot sign-extended from its width (an in-band NULL stays in band)
+ *   arg_is_fp DOUBLE, not AVG       the slot's 8 bytes
+ *   arg_is_fp FLOAT, not AVG        the float in the slot's low 4 bytes widened to double; with skip_null,
+ *                                   HDK_NULL_FLOAT_BITS becomes HDK_NULL_DOUBLE_BITS
+ *   AVG                             pair_to_double (omniscidb/ResultSet/ResultSetBufferAccessors.h:168-190):
+ *                                   double(dividend) / double(count), dividend = (double)int64 sum, the double's bits or
+ *                                   the widened float; HDK_NULL_DOUBLE_BITS when count == 0
+ * `entry_count` is that of THIS buffer and may differ from plan->entry_count (a reduced baseline table);  `init_vals` is
+ * the HOST array of hdk_hip_reduce_buffers (keyless emptiness).  `*row_count` (device) always receives the TRUE number of
+ * non-empty entries; rows at or beyond `capacity` are not written, and nothing outside [0, min(rows, capacity)) of a
+ * column is touched.  out_cols == NULL: count only.  `workspace`: hdk_hip_result_columns_workspace_bytes(entry_count)
+ * bytes of device memory (host arithmetic only: 4 bytes per tile of 4 096 entries), or NULL -- the library then takes it
+ * from the stream's memory pool (hipMallocAsync), as the fused join build does.  Asynchronous on `stream`; the host
+ * never waits.
+ * ---------------------------------------------------------------------------------------- */
+size_t hdk_hip_result_columns_workspace_bytes(uint32_t entry_count);
+int32_t hdk_hip_columnarize_result(const hdk_hip_plan* plan, const int64_t* buf, uint32_t entry_count,
+                                   const int64_t* init_vals, int64_t* out_cols, uint64_t capacity, uint64_t* row_count,
+                                   void* workspace, size_t workspace_bytes, int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Environment switches (MI355X addition; no reference counterpart: the reference's knobs are Config fields,
  * Shared/Config.h).  libhdk_hip.so reads its HDK_HIP_* variables (tests and A/B measurements, none needed
  * in production) ONCE per process, at the first launch that asks for one -- never per launch, so a host that calls
