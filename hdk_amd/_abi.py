@@ -15,6 +15,8 @@ MAX_JOINS = 2
 MAX_JOIN_KEYS = 3
 MAX_EXPR_STEPS = 3
 MAX_FILTER_OPS = 16
+MAX_ORDER_ENTRIES = 8
+SORT_NO_SELECT = 1  # hdk_hip_sort_columns flags
 F_AND, F_OR, F_NOT = 64, 65, 66
 PLAN_ABI = 4
 
@@ -143,6 +145,12 @@ class ExchangeShape(C.Structure):
                 ("sub_slab_tuples", C.c_uint64), ("segment_header_bytes", C.c_uint64), ("segment_bytes", C.c_uint64),
                 ("rows_bound", C.c_uint64), ("scatter_workspace_bytes", C.c_uint64),
                 ("aggregate_workspace_bytes", C.c_uint64)]
+
+
+class OrderEntry(C.Structure):
+    """hdk_hip_order_entry: one ORDER BY entry over dense result columns (hdk_hip_sort_columns)."""
+    _fields_ = [("col", C.c_int32), ("is_desc", C.c_uint8), ("nulls_first", C.c_uint8), ("is_fp", C.c_uint8),
+                ("nullable", C.c_uint8), ("null_bits", C.c_int64)]
 
 
 class KernelOptions(C.Structure):

@@ -23,7 +23,8 @@ from . import result_set
 from ._lib import HdkHipError, check, lib, sync_switches
 from .hip_mgr import DeviceBuffer, HipMgr
 from .ir import QueryMustRunOnCpu, QueryUnit
-from .plan import DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, CompiledPlan, columnar_init_vals, compact_init_vals, compile_query, eff_key_count
+from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, CompiledPlan, columnar_init_vals, compact_init_vals, compile_query,
+                   eff_key_count, resolve_order_by)
 from .storage import ArrowStorage
 
 
@@ -134,6 +135,49 @@ class DeviceColumns:
 
     def row_count(self):
         return self.num_rows
+
+    def sort(self, order_by, limit: Optional[int] = None, offset: int = 0, no_select: bool = False) -> "DeviceColumns":
+        """ORDER BY `order_by` LIMIT `limit` OFFSET `offset` on the device (hdk_hip_sort_columns; the reference's
+        ResultSet::sort, QE/ResultSetSort.cpp:64-188) -> a new DeviceColumns that owns a block of exactly the output
+        rows; this object stays valid.  `order_by`: ir.OrderEntry items (target index or output name) or resolved
+        (target index, desc, nulls_first) triples.  Ties keep their order in this object.  Without `order_by` the result
+        is rows [offset, offset + limit) as they are: one copy per column, no sort.  no_select=True forces the full sort
+        where a LIMIT would select the candidates first (HDK_HIP_SORT_NO_SELECT)."""
+        if (limit is not None and limit < 0) or offset < 0:
+            raise ValueError("limit and offset must not be negative")
+        cp = self.compiled
+        nt = int(cp.plan.num_targets)
+        entries = [e if isinstance(e, tuple) else None for e in order_by]
+        if any(e is None for e in entries):
+            entries = resolve_order_by(cp.out_cols, nt, list(order_by))
+        n = self.num_rows
+        after = max(n - int(offset), 0)
+        out_rows = after if not limit else min(int(limit), after)
+        if limit == 0:  # (LIMIT 0 is no row; the C ABI's 0 means "no limit")
+            out_rows = 0
+        if out_rows == 0:
+            return DeviceColumns(cp, self.mgr, self.device_id, None, 0, 0, self.error_code)
+        if self.block is None or not self.block.ptr:
+            raise ValueError("the columns have been freed")
+        block = self.mgr.alloc(nt * out_rows * 8, self.device_id)
+        try:
+            if not entries:
+                for t in range(nt):
+                    self.mgr.copyDeviceToDevice(block.ptr + t * out_rows * 8, self.device_ptr(t) + int(offset) * 8,
+                                                   out_rows * 8, self.device_id, self.device_id)
+            else:
+                arr = (A.OrderEntry * len(entries))()
+                for i, (t, desc, nulls_first) in enumerate(entries):
+                    is_fp, nullable, null_bits = result_set.dense_column_null(cp, t)
+                    arr[i] = A.OrderEntry(t, int(desc), int(nulls_first), int(is_fp), int(nullable), A.to_i64(null_bits))
+                check(lib().hdk_hip_sort_columns(self.block.ptr, self.capacity, nt, n, arr, len(entries), int(offset),
+                                                 out_rows if limit else 0, A.SORT_NO_SELECT if no_select else 0, block.ptr,
+                                                 out_rows, None, None, 0, self.device_id, None))
+            self.mgr.synchronizeStream(self.device_id)
+        except Exception:
+            block.free()
+            raise
+        return DeviceColumns(cp, self.mgr, self.device_id, block, out_rows, out_rows, self.error_code)
 
     def free(self):
         if self.block is not None:
@@ -629,6 +673,10 @@ class Executor:
             raise QueryMustRunOnCpu("hdk_amd ships the GPU path only; run device_type='CPU' on HDK itself")
         if result not in ("buffer", "columns"):
             raise ValueError(f"result must be 'buffer' or 'columns', not {result!r}")
+        sq = q.query if isinstance(q, CompiledPlan) else q
+        sorts = bool(sq.order_by) or sq.limit is not None or bool(sq.offset)
+        if sorts and result == "buffer":
+            raise ValueError("order_by / limit / offset need result='columns': a hash-table buffer has no row order")
         # A QueryUnit whose open-addressing table the PLANNER sized (no baseline_entry_count): running out of slots means
         # the estimate was wrong (stale statistics, a key from an inner column) -- RelAlgExecutor::handleOutOfMemoryRetry
         # (QE/RelAlgExecutor.cpp:1713-1747) re-runs with a doubled max_groups_buffer_entry_guess, at most twice more, and
@@ -640,7 +688,13 @@ class Executor:
             try:
                 if result == "columns":
                     step.enqueue()
-                    return step.fetch_columns()
+                    cols = step.fetch_columns()
+                    if not sorts:
+                        return cols
+                    try:  # the query's SortInfo, applied where the columns are; the unsorted block is handed back
+                        return cols.sort(step.cp.order_by, sq.limit, sq.offset)
+                    finally:
+                        cols.free()
                 return step.run()
             except HdkHipError as e:
                 if e.code != A.ERR_OUT_OF_SLOTS or step.cp.plan.query_kind != A.Q_BASELINE_HASH or retries_left == 0:

@@ -186,4 +186,23 @@ inline void columnarize_result_on_device(const hdk_hip_plan& plan, const int64_t
                                    row_count_dev, workspace, workspace_bytes, device_id, nullptr));
 }
 
+// ResultSet::sort for a result whose dense columns are on the device: what doBaselineSort (QueryEngine/ResultSetSort.cpp:
+// 64-188) does with ResultSetSortImpl.cu / TopKSort.cu.  `order` is RelAlgExecutionUnit::sort_info.order_entries restated
+// (col = tle_no - 1; is_fp / nullable / null_bits from the target's type), `limit` / `offset` are SortInfo's (0 = no
+// limit).  Column t of the input starts at cols + t * capacity, of the output at out_cols + t * out_capacity;
+// perm_out (device, may be null) receives the permutation.  `workspace` comes from the BufferProvider
+// (sort_columns_workspace_bytes(num_rows, num_order) bytes) or is null (the stream's memory pool).  Synchronises the
+// stream while it runs (include/hdk_hip.h); the output is complete when the stream has drained.
+inline size_t sort_columns_workspace_bytes(const size_t num_rows, const int num_order) {
+  return hdk_hip_sort_columns_workspace_bytes(static_cast<uint64_t>(num_rows), num_order);
+}
+inline void sort_columns_on_device(const int64_t* cols, const size_t capacity, const int num_cols, const size_t num_rows,
+                                   const hdk_hip_order_entry* order, const int num_order, const size_t offset,
+                                   const size_t limit, int64_t* out_cols, const size_t out_capacity, uint32_t* perm_out,
+                                   int8_t* workspace, const size_t workspace_bytes, const int device_id) {
+  check(hdk_hip_sort_columns(cols, static_cast<uint64_t>(capacity), num_cols, static_cast<uint64_t>(num_rows), order, num_order,
+                             static_cast<uint64_t>(offset), static_cast<uint64_t>(limit), 0u, out_cols,
+                             static_cast<uint64_t>(out_capacity), perm_out, workspace, workspace_bytes, device_id, nullptr));
+}
+
 }  // namespace hip_rt

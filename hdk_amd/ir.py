@@ -215,6 +215,15 @@ class JoinSpec:
         return list(self.inner_col) if isinstance(self.inner_col, (list, tuple)) else [self.inner_col]
 
 
+@dataclass(frozen=True)
+class OrderEntry:
+    """One ORDER BY entry (hdk::ir::OrderEntry, omniscidb/IR/Node.h: tle_no, is_desc, nulls_first): `target` is the
+    target's 0-based index or its output name."""
+    target: Union[int, str]
+    desc: bool = False
+    nulls_first: bool = False
+
+
 @dataclass
 class QueryUnit:
     """What one execution step needs (cf. RelAlgExecutionUnit)."""
@@ -229,3 +238,7 @@ class QueryUnit:
     bigint_count: bool = False  # Config.exec.group_by.bigint_count (omniscidb/Shared/Config.h:44)
     baseline_entry_count: Optional[int] = None  # max_groups_buffer_entry_count override
     force_baseline: bool = False
+    # SortInfo (RelAlgExecutionUnit::sort_info): applied to the dense result columns on the device (result="columns")
+    order_by: List[OrderEntry] = field(default_factory=list)
+    limit: Optional[int] = None
+    offset: int = 0

@@ -336,6 +336,7 @@ class CompiledPlan:
     key_types: List[Type]
     buffer_bytes: int
     key_ranges: List[Range] = field(default_factory=list)
+    order_by: List[Tuple[int, bool, bool]] = field(default_factory=list)  # (target index, desc, nulls_first), resolved
 
     @property
     def entry_count(self):
@@ -692,11 +693,43 @@ def compile_projection(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
                         out_cols=out_cols, key_types=[], buffer_bytes=buffer_bytes, key_ranges=[])
 
 
+def _has_sort_info(q: QueryUnit) -> bool:
+    return bool(q.order_by) or q.limit is not None or bool(q.offset)
+
+
+def resolve_order_by(out_cols: List["OutCol"], num_targets: int, order_by) -> List[Tuple[int, bool, bool]]:
+    """ORDER BY entries -> (target index, desc, nulls_first).  A name is a target's output name.  An unknown name or
+    index is a ValueError; more entries than the library takes, or a dictionary-encoded key (the dense column holds
+    string ids, whose order is not the strings'), must run on the CPU."""
+    if len(order_by) > A.MAX_ORDER_ENTRIES:
+        raise QueryMustRunOnCpu("more than %d ORDER BY entries" % A.MAX_ORDER_ENTRIES)
+    by_name = {oc.name: oc for oc in out_cols}
+    by_idx = {oc.target_idx: oc for oc in out_cols}
+    res = []
+    for e in order_by:
+        if isinstance(e.target, str):
+            if e.target not in by_name:
+                raise ValueError(f"ORDER BY names no target: {e.target!r}")
+            oc = by_name[e.target]
+        else:
+            if isinstance(e.target, bool) or not 0 <= int(e.target) < num_targets:
+                raise ValueError(f"ORDER BY target index {e.target!r} outside 0..{num_targets - 1}")
+            oc = by_idx[int(e.target)]
+        if oc.kind == "key" and oc.dictionary is not None:
+            raise QueryMustRunOnCpu(f"ORDER BY a dictionary-encoded key ({oc.name}): id order is not string order")
+        res.append((oc.target_idx, bool(e.desc), bool(e.nulls_first)))
+    return res
+
+
 def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
     from .ir import Proj
+    if q.limit is not None and q.limit < 0 or q.offset < 0:
+        raise ValueError("limit and offset must not be negative")
     if q.targets and all(isinstance(t, Proj) for t in q.targets):
         if q.groupby:
             raise QueryMustRunOnCpu("projection targets with GROUP BY")
+        if _has_sort_info(q):
+            raise QueryMustRunOnCpu("ORDER BY / LIMIT / OFFSET on a projection: it has no dense device columns")
         return compile_projection(storage, q)
     if any(isinstance(t, Proj) for t in q.targets):
         raise QueryMustRunOnCpu("mixing projections and aggregates")
@@ -1016,11 +1049,16 @@ def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
         c.table = slot
         c.width = ct.size
         _fill_col_kind(storage, tn, cn, ct, c)
+    order_by = []
+    if _has_sort_info(q):
+        if kind == A.Q_NON_GROUPED:
+            raise QueryMustRunOnCpu("ORDER BY / LIMIT / OFFSET on a non-grouped query: it has no dense device columns")
+        order_by = resolve_order_by(out_cols, int(p.num_targets), q.order_by)
     return CompiledPlan(plan=p, query=q, init_vals=np.array(init_vals, dtype=np.int64),
                         slot_widths=slot_widths, input_cols=list(b.cols),
                         inner_tables=[t.name for t in b.inner], join_infos=join_infos,
                         out_cols=out_cols, key_types=key_types, buffer_bytes=buffer_bytes,
-                        key_ranges=key_ranges)
+                        key_ranges=key_ranges, order_by=order_by)
 
 
 # ---------------------------------------------------------------------------------------------

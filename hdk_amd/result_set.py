@@ -240,6 +240,26 @@ def _column_values(cp: CompiledPlan, oc, vals: np.ndarray, cnt, w: int, dense: b
     return col
 
 
+def dense_column_null(cp: CompiledPlan, target_idx: int):
+    """(is_fp, nullable, null_bits) of target `target_idx`'s dense device column: how its 8-byte words compare (as doubles or
+    as int64) and which word, if any, is its in-band NULL -- by the rules _column_values(dense=True) reads the column with."""
+    tg = cp.plan.targets[target_idx]
+    if tg.agg == A.AGG_ID:
+        kt = cp.key_types[tg.key_idx]
+        nullv = kt.null_as_int64_or_double_bits() if kt.is_fp else kt.null_value()
+        return bool(kt.is_fp), bool(kt.nullable), A.to_i64(nullv)
+    if tg.agg == A.AGG_COUNT:
+        return False, False, 0
+    float_slot = tg.arg_is_fp == A.FP_SLOT_FLOAT
+    if tg.agg == A.AGG_AVG or float_slot:
+        return True, bool(tg.agg == A.AGG_AVG or tg.skip_null), A.NULL_DOUBLE_BITS
+    first_slot = sum(2 if cp.plan.targets[t].agg == A.AGG_AVG else 1 for t in range(target_idx))
+    nullv = int(tg.null_val)
+    if cp.slot_widths[first_slot] == 4:
+        nullv = int(np.int64(nullv).astype(np.int32))
+    return bool(tg.arg_is_fp), bool(tg.skip_null), nullv
+
+
 def dense_to_columns(cp: CompiledPlan, dense: List[np.ndarray]) -> Dict[str, list]:
     """to_columns() from dense device columns: dense[t] holds target t's 8-byte values (int64 words), one per group in
     entry order, as hdk_hip_columnarize_result writes them.  The same names, order, NULLs, dictionary strings and

@@ -600,6 +600,55 @@ int32_t hdk_hip_columnarize_result(const hdk_hip_plan* plan, const int64_t* buf,
                                    void* workspace, size_t workspace_bytes, int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * ORDER BY / LIMIT / OFFSET over dense result columns on the device.
+ * Replaces, for a result whose columns sit in HBM, ResultSet::sort with doBaselineSort and its GPU sorts
+ * (omniscidb/QueryEngine/ResultSetSort.cpp:64-188, ResultSetSortImpl.cu, TopKSort.cu); the order entries, limit and
+ * offset are RelAlgExecutionUnit's SortInfo.  Input: `num_cols` columns of `num_rows` 8-byte words, column t at
+ * cols + t * capacity, NULLs in band -- what hdk_hip_columnarize_result writes.  Output: column t at
+ * out_cols + t * out_capacity.  With out_rows = min(limit ? limit : infinity, num_rows > offset ? num_rows - offset : 0)
+ * (host arithmetic, hence not returned), rows [0, out_rows) of every output column receive input rows perm[offset + r] and
+ * perm_out[r] (when not NULL) that input row index -- the reference's permutation buffer.  Nothing at or beyond out_rows is
+ * written, the input is not modified, and out_cols must not overlap cols.
+ * Order: ResultSetComparator (ResultSetSort.cpp:329-480), entry by entry from the first: both NULL -> next entry; one
+ * NULL -> nulls_first decides, whatever is_desc says; equal words -> next entry; otherwise (l < r) != is_desc, compared as
+ * int64 or, with is_fp, as doubles.  A word is NULL when the entry is nullable and the word equals null_bits.
+ * Rows equal on every entry come out in ascending input row index (the reference leaves the order among ties open: a
+ * stable result is one of its valid results, and it is the same on every run).  Doubles are ordered by the usual
+ * order-preserving bit transform, which differs from operator< in two places: -0.0 comes BEFORE +0.0 (the reference calls
+ * them a tie), and NaNs are ordered by bit pattern beyond the infinities (sign bit set: before -inf; clear: after +inf).
+ * A LIMIT with offset + limit <= num_rows / 8 first selects the candidate rows by the first entry (radix select, ties at
+ * the threshold kept) and sorts only those; the result is word for word that of the full sort, which
+ * HDK_HIP_SORT_NO_SELECT forces.
+ * Errors, all found before any device is touched (HDK_HIP_ERR_INVALID_ARG with a message): a NULL cols / order / out_cols,
+ * num_order outside 1..HDK_HIP_MAX_ORDER_ENTRIES, an entry's col outside [0, num_cols), num_rows >= 2^32, num_rows >
+ * capacity, out_capacity < out_rows, overlapping blocks, a workspace that is too small.  num_rows == 0 or out_rows == 0:
+ * HDK_HIP_OK, nothing is launched.
+ * `workspace`: hdk_hip_sort_columns_workspace_bytes(num_rows, num_order) bytes of device memory (host arithmetic only:
+ * two (8-byte key, 4-byte row) pairs and 1/4 byte of digit counters per row, plus 4 KiB), or NULL -- the library then takes
+ * it from the stream's memory pool (hipMallocAsync), as hdk_hip_columnarize_result does.
+ * SYNCHRONISES `stream`: once per order entry the host reads 16 bytes back (which digits of the keys differ at all, so
+ * that only those radix passes are launched), and once more on the selection path (the number of candidates).  The final
+ * passes and the gather are asynchronous: the output is complete when `stream` has drained.
+ * ---------------------------------------------------------------------------------------- */
+#define HDK_HIP_MAX_ORDER_ENTRIES 8
+#define HDK_HIP_SORT_NO_SELECT 1u /* flags: always the full sort, never the top-N selection (tests, A/B) */
+
+typedef struct hdk_hip_order_entry {
+  int32_t col;         /* 0-based column = target index (the reference's tle_no - 1) */
+  uint8_t is_desc;
+  uint8_t nulls_first;
+  uint8_t is_fp;       /* words are doubles, compared as doubles; else int64 */
+  uint8_t nullable;    /* 0: null_bits is an ordinary value */
+  int64_t null_bits;   /* the column's in-band NULL as the dense column holds it */
+} hdk_hip_order_entry;
+
+size_t hdk_hip_sort_columns_workspace_bytes(uint64_t num_rows, int32_t num_order);
+int32_t hdk_hip_sort_columns(const int64_t* cols, uint64_t capacity, int32_t num_cols, uint64_t num_rows,
+                             const hdk_hip_order_entry* order, int32_t num_order, uint64_t offset, uint64_t limit,
+                             uint32_t flags, int64_t* out_cols, uint64_t out_capacity, uint32_t* perm_out, void* workspace,
+                             size_t workspace_bytes, int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Environment switches (MI355X addition; no reference counterpart: the reference's knobs are Config fields,
  * Shared/Config.h).  libhdk_hip.so reads its HDK_HIP_* variables (tests and A/B measurements, none needed
  * in production) ONCE per process, at the first launch that asks for one -- never per launch, so a host that calls
