@@ -16,6 +16,7 @@ MAX_JOIN_KEYS = 3
 MAX_EXPR_STEPS = 3
 MAX_FILTER_OPS = 16
 MAX_ORDER_ENTRIES = 8
+MAX_HAVING_LEAVES = 8
 SORT_NO_SELECT = 1  # hdk_hip_sort_columns flags
 F_AND, F_OR, F_NOT = 64, 65, 66
 PLAN_ABI = 4
@@ -151,6 +152,16 @@ class OrderEntry(C.Structure):
     """hdk_hip_order_entry: one ORDER BY entry over dense result columns (hdk_hip_sort_columns)."""
     _fields_ = [("col", C.c_int32), ("is_desc", C.c_uint8), ("nulls_first", C.c_uint8), ("is_fp", C.c_uint8),
                 ("nullable", C.c_uint8), ("null_bits", C.c_int64)]
+
+
+class HavingLeaf(C.Structure):
+    """hdk_hip_having_leaf: one comparison of a HAVING predicate over dense result columns (hdk_hip_filter_columns):
+    column lhs_col <cmp> column rhs_col or the literal rhs_lit.  A side is NULL when it is nullable and its word equals
+    null_bits (a literal never is); cmp_fp compares as doubles, an int64 side converted with (double)."""
+    _fields_ = [("lhs_col", C.c_int32), ("rhs_col", C.c_int32), ("cmp", C.c_uint8), ("rhs_is_col", C.c_uint8),
+                ("cmp_fp", C.c_uint8), ("lhs_is_fp", C.c_uint8), ("lhs_nullable", C.c_uint8), ("rhs_is_fp", C.c_uint8),
+                ("rhs_nullable", C.c_uint8), ("pad_", C.c_uint8), ("lhs_null_bits", C.c_int64),
+                ("rhs_null_bits", C.c_int64), ("rhs_lit", C.c_int64)]
 
 
 class KernelOptions(C.Structure):

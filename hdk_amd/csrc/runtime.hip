@@ -173,7 +173,7 @@ extern "C" int32_t hdk_hip_set_interrupt(int32_t device_id, int32_t value) {
 extern "C" {
 
 const char* hdk_hip_last_error(void) { return tl_error; }
-int32_t hdk_hip_version(void) { return 1002; }
+int32_t hdk_hip_version(void) { return 1003; }
 
 int32_t hdk_hip_mgr_get_device_count(int32_t* count) {
   HDK_REQUIRE(count, "count is NULL");

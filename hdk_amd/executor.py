@@ -23,8 +23,8 @@ from . import result_set
 from ._lib import HdkHipError, check, lib, sync_switches
 from .hip_mgr import DeviceBuffer, HipMgr
 from .ir import QueryMustRunOnCpu, QueryUnit
-from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, CompiledPlan, columnar_init_vals, compact_init_vals, compile_query,
-                   eff_key_count, resolve_order_by)
+from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, CompiledPlan, Having, columnar_init_vals, compact_init_vals,
+                   compile_query, eff_key_count, resolve_having, resolve_order_by)
 from .storage import ArrowStorage
 
 
@@ -178,6 +178,63 @@ class DeviceColumns:
             block.free()
             raise
         return DeviceColumns(cp, self.mgr, self.device_id, block, out_rows, out_rows, self.error_code)
+
+    FILTER_ONE_CALL_BYTES = 64 << 20  # as PreparedStep.COLUMNS_ONE_CALL_BYTES
+
+    def filter(self, having) -> "DeviceColumns":
+        """HAVING on the device (hdk_hip_filter_columns; the reference's filter step over the previous step's result) ->
+        a new DeviceColumns with the rows on which the predicate is TRUE, in this object's order; this object stays
+        valid.  `having`: a Cond tree or a list of them (a conjunction) over ir.TargetRef / ir.Lit, or the resolved
+        plan.Having.  Sizing as fetch_columns(): up to 64 MiB of worst-case output one call writes into a block of
+        num_rows rows per column; above that the passing rows are counted first (out_cols = NULL) and the block holds
+        exactly those.  One stream synchronisation per call, to read row_count back."""
+        cp = self.compiled
+        if not isinstance(having, Having):
+            having = resolve_having(cp, list(having) if isinstance(having, (list, tuple)) else [having])
+        nt = int(cp.plan.num_targets)
+        n = self.num_rows
+        if n == 0 or having is None:
+            if having is None and n:
+                return self.sort([])  # no predicate: every row, copied
+            return DeviceColumns(cp, self.mgr, self.device_id, None, 0, 0, self.error_code)
+        if self.block is None or not self.block.ptr:
+            raise ValueError("the columns have been freed")
+        leaves = (A.HavingLeaf * len(having.leaves))()
+        for i, lf in enumerate(having.leaves):
+            leaves[i] = A.HavingLeaf(lf.lhs_col, lf.rhs_col, lf.cmp, int(lf.rhs_is_col), int(lf.cmp_fp), int(lf.lhs_is_fp),
+                                     int(lf.lhs_nullable), int(lf.rhs_is_fp), int(lf.rhs_nullable), 0,
+                                     A.to_i64(lf.lhs_null_bits), A.to_i64(lf.rhs_null_bits), A.to_i64(lf.rhs_lit))
+        ops = (C.c_uint8 * max(len(having.prog), 1))(*having.prog)
+        d_rows = self.mgr.alloc(8, self.device_id)
+        block = None
+
+        def call(out_ptr, capacity):
+            check(lib().hdk_hip_filter_columns(self.block.ptr, self.capacity, nt, n, leaves, len(having.leaves), ops,
+                                               len(having.prog), out_ptr, capacity, d_rows.ptr, None, None, 0,
+                                               self.device_id, None))
+            self.mgr.synchronizeStream(self.device_id)
+            return int(self.mgr.to_host(d_rows.ptr, 8, self.device_id, np.uint64)[0])
+
+        try:
+            if nt * n * 8 <= self.FILTER_ONE_CALL_BYTES:
+                block = self.mgr.alloc(nt * n * 8, self.device_id)
+                capacity = n
+                rows = call(block.ptr, capacity)
+            else:
+                rows = capacity = call(None, 0)
+                if rows:
+                    block = self.mgr.alloc(nt * rows * 8, self.device_id)
+                    call(block.ptr, capacity)
+            if rows == 0 and block is not None:
+                block.free()
+                block, capacity = None, 0
+        except Exception:
+            if block is not None:
+                block.free()
+            raise
+        finally:
+            d_rows.free()
+        return DeviceColumns(cp, self.mgr, self.device_id, block, capacity, rows, self.error_code)
 
     def free(self):
         if self.block is not None:
@@ -677,6 +734,8 @@ class Executor:
         sorts = bool(sq.order_by) or sq.limit is not None or bool(sq.offset)
         if sorts and result == "buffer":
             raise ValueError("order_by / limit / offset need result='columns': a hash-table buffer has no row order")
+        if sq.having and result == "buffer":
+            raise ValueError("having needs result='columns': it filters the dense result columns, not a hash-table buffer")
         # A QueryUnit whose open-addressing table the PLANNER sized (no baseline_entry_count): running out of slots means
         # the estimate was wrong (stale statistics, a key from an inner column) -- RelAlgExecutor::handleOutOfMemoryRetry
         # (QE/RelAlgExecutor.cpp:1713-1747) re-runs with a doubled max_groups_buffer_entry_guess, at most twice more, and
@@ -689,9 +748,15 @@ class Executor:
                 if result == "columns":
                     step.enqueue()
                     cols = step.fetch_columns()
+                    if step.cp.having is not None:  # HAVING, then the query's SortInfo, applied where the columns are;
+                        try:                        # every intermediate block is handed back
+                            kept = cols.filter(step.cp.having)
+                        finally:
+                            cols.free()
+                        cols = kept
                     if not sorts:
                         return cols
-                    try:  # the query's SortInfo, applied where the columns are; the unsorted block is handed back
+                    try:
                         return cols.sort(step.cp.order_by, sq.limit, sq.offset)
                     finally:
                         cols.free()

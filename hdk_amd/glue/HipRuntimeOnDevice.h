@@ -205,4 +205,26 @@ inline void sort_columns_on_device(const int64_t* cols, const size_t capacity, c
                              static_cast<uint64_t>(out_capacity), perm_out, workspace, workspace_bytes, device_id, nullptr));
 }
 
+// HAVING for a result whose dense columns are on the device: the reference's filter step over the previous step's result
+// (a temporary table of ColumnarResults), with DEF_CMP_NULLABLE* comparisons under logical_and / logical_or / logical_not
+// (QueryEngine/RuntimeFunctions.cpp:83-117, :355-384).  `leaves` restate the comparisons (target index, hdk_hip_cmp, a
+// literal or a second target, and per side is_fp / nullable / null_bits from the target's type), `ops` is the postfix
+// program over them in the encoding of hdk_hip_plan::filter_ops (num_ops == 0: the conjunction of all leaves).  Rows on
+// which the predicate is TRUE are written in input order to out_cols + t * out_capacity; *row_count_dev (device) always
+// receives their true number, rows at or beyond out_capacity are not written, out_cols == nullptr counts only; perm_out
+// (device, may be null) receives the input row of each output row.  `workspace` comes from the BufferProvider
+// (filter_columns_workspace_bytes(num_rows) bytes) or is null (the stream's memory pool).  Asynchronous on the device's
+// stream, like columnarize_result_on_device: the host never waits.
+inline size_t filter_columns_workspace_bytes(const size_t num_rows) {
+  return hdk_hip_filter_columns_workspace_bytes(static_cast<uint64_t>(num_rows));
+}
+inline void filter_columns_on_device(const int64_t* cols, const size_t capacity, const int num_cols, const size_t num_rows,
+                                     const hdk_hip_having_leaf* leaves, const int num_leaves, const uint8_t* ops,
+                                     const int num_ops, int64_t* out_cols, const size_t out_capacity, uint64_t* row_count_dev,
+                                     uint32_t* perm_out, int8_t* workspace, const size_t workspace_bytes, const int device_id) {
+  check(hdk_hip_filter_columns(cols, static_cast<uint64_t>(capacity), num_cols, static_cast<uint64_t>(num_rows), leaves, num_leaves,
+                               ops, num_ops, out_cols, static_cast<uint64_t>(out_capacity), row_count_dev, perm_out, workspace,
+                               workspace_bytes, device_id, nullptr));
+}
+
 }  // namespace hip_rt

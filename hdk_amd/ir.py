@@ -120,6 +120,14 @@ class Lit(Expr):
 
 
 @dataclass(frozen=True)
+class TargetRef(Expr):
+    """A target of the same step, by 0-based index or output name: what a HAVING comparison reads (the reference's
+    filter step over the previous step's result names that result's columns).  Valid only inside QueryUnit.having:
+    compile_query raises a ValueError for one in quals, groupby, targets or join keys."""
+    target: Union[int, str]
+
+
+@dataclass(frozen=True)
 class BinOp(Expr):
     op: str  # + - * / %
     lhs: Expr
@@ -242,3 +250,7 @@ class QueryUnit:
     order_by: List[OrderEntry] = field(default_factory=list)
     limit: Optional[int] = None
     offset: int = 0
+    # HAVING: a conjunction of Cmp / And / Or / Not trees whose leaves are Cmp(TargetRef, op, Lit) or
+    # Cmp(TargetRef, op, TargetRef) (a literal on the left is swapped, the operator mirrored); applied to the dense result
+    # columns on the device before order_by / limit / offset (result="columns")
+    having: List[Cond] = field(default_factory=list)

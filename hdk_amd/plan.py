@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _abi as A
 from .ir import (Agg, And, BinOp, Cast, Cmp, ColRef, Expr, ExtractYear, KeyRef, Lit, Not, Or, QueryMustRunOnCpu,
-                 QueryUnit, Type)
+                 QueryUnit, TargetRef, Type)
 from .storage import ArrowStorage, Table
 
 BASELINE_THRESHOLD = 1_000_000  # Config.exec.group_by.baseline_threshold (Shared/Config.h:51)
@@ -337,6 +337,7 @@ class CompiledPlan:
     buffer_bytes: int
     key_ranges: List[Range] = field(default_factory=list)
     order_by: List[Tuple[int, bool, bool]] = field(default_factory=list)  # (target index, desc, nulls_first), resolved
+    having: Optional["Having"] = None  # the query's HAVING, resolved (resolve_having); None: no HAVING
 
     @property
     def entry_count(self):
@@ -721,8 +722,151 @@ def resolve_order_by(out_cols: List["OutCol"], num_targets: int, order_by) -> Li
     return res
 
 
+@dataclass(frozen=True)
+class HavingLeaf:
+    """One comparison of a resolved HAVING: the fields of hdk_hip_having_leaf (include/hdk_hip.h)."""
+    lhs_col: int
+    cmp: int  # hdk_hip_cmp
+    rhs_is_col: bool
+    rhs_col: int
+    rhs_lit: int  # int64, or a double's bits (rhs_is_fp)
+    cmp_fp: bool
+    lhs_is_fp: bool
+    lhs_nullable: bool
+    lhs_null_bits: int
+    rhs_is_fp: bool
+    rhs_nullable: bool
+    rhs_null_bits: int
+
+
+@dataclass
+class Having:
+    """A resolved HAVING: the distinct comparisons and the postfix program over them in the encoding of
+    hdk_hip_plan::filter_ops (empty: the plain conjunction of all leaves)."""
+    leaves: List[HavingLeaf]
+    prog: List[int]
+
+
+_MIRROR = {A.CMP_EQ: A.CMP_EQ, A.CMP_NE: A.CMP_NE, A.CMP_LT: A.CMP_GT, A.CMP_GT: A.CMP_LT, A.CMP_LE: A.CMP_GE,
+           A.CMP_GE: A.CMP_LE}
+
+
+def resolve_having(cp: CompiledPlan, having) -> Optional[Having]:
+    """HAVING conditions (a conjunction of Cmp / And / Or / Not trees over TargetRef and Lit) -> Having, against the dense
+    columns of `cp`.  Per side is_fp / nullable / null_bits are result_set.dense_column_null's; the comparison is made in
+    doubles when either side is fp or the literal is a float.  An unknown target name or index is a ValueError; what the
+    library's call cannot express (a dictionary-encoded or decimal target, arithmetic inside a leaf, more than
+    MAX_HAVING_LEAVES comparisons, a program beyond MAX_FILTER_OPS) must run on the CPU."""
+    from .result_set import dense_column_null
+    having = list(having)
+    if not having:
+        return None
+    kind = cp.plan.query_kind
+    if kind != A.Q_PERFECT_HASH and kind != A.Q_BASELINE_HASH:
+        raise QueryMustRunOnCpu("HAVING on a step that is not a group-by: it has no dense device columns")
+    nt = int(cp.plan.num_targets)
+    by_name = {oc.name: oc for oc in cp.out_cols}
+    by_idx = {oc.target_idx: oc for oc in cp.out_cols}
+
+    def target(e: TargetRef) -> int:
+        if isinstance(e.target, str):
+            if e.target not in by_name:
+                raise ValueError(f"HAVING names no target: {e.target!r}")
+            oc = by_name[e.target]
+        else:
+            if isinstance(e.target, bool) or not 0 <= int(e.target) < nt:
+                raise ValueError(f"HAVING target index {e.target!r} outside 0..{nt - 1}")
+            oc = by_idx[int(e.target)]
+        if oc.dictionary is not None or oc.type.kind == "dict":
+            raise QueryMustRunOnCpu(f"HAVING on a dictionary-encoded target ({oc.name}): the dense column holds string ids")
+        if oc.type.kind == "decimal" or oc.scale:
+            raise QueryMustRunOnCpu(f"HAVING on a decimal target ({oc.name}): the dense column holds scaled values")
+        return oc.target_idx
+
+    def leaf(c: Cmp) -> HavingLeaf:
+        if c.op not in _CMP:
+            raise ValueError(f"HAVING: unknown comparison operator {c.op!r}")
+        lhs, rhs, cmp = c.lhs, c.rhs, _CMP[c.op]
+        if isinstance(lhs, Lit) and isinstance(rhs, TargetRef):  # literal on the left: swapped, the operator mirrored
+            lhs, rhs, cmp = rhs, lhs, _MIRROR[cmp]
+        if not isinstance(lhs, TargetRef) or not isinstance(rhs, (TargetRef, Lit)):
+            raise QueryMustRunOnCpu(f"HAVING compares a target with a literal or a target; arithmetic inside a comparison "
+                                    f"({c!r}) is outside the fixed kernel library")
+        lt = target(lhs)
+        l_fp, l_nullable, l_null = dense_column_null(cp, lt)
+        if isinstance(rhs, TargetRef):
+            rt = target(rhs)
+            r_fp, r_nullable, r_null = dense_column_null(cp, rt)
+            return HavingLeaf(lt, cmp, True, rt, 0, bool(l_fp or r_fp), bool(l_fp), bool(l_nullable), A.to_i64(l_null),
+                              bool(r_fp), bool(r_nullable), A.to_i64(r_null))
+        v = rhs.value
+        if isinstance(v, (bool, np.bool_)):
+            v = int(v)
+        if isinstance(v, (float, np.floating)) or l_fp:
+            bits = struct.unpack("<q", struct.pack("<d", float(v)))[0]
+            return HavingLeaf(lt, cmp, False, 0, bits, True, bool(l_fp), bool(l_nullable), A.to_i64(l_null), True, False, 0)
+        if not isinstance(v, (int, np.integer)) or not -2**63 <= int(v) < 2**63:
+            raise QueryMustRunOnCpu(f"HAVING literal {v!r} is no int64 or double")
+        return HavingLeaf(lt, cmp, False, 0, int(v), False, False, bool(l_nullable), A.to_i64(l_null), False, False, 0)
+
+    leaves: List[HavingLeaf] = []
+    prog: List[int] = []
+
+    def emit(c):
+        if isinstance(c, Cmp):
+            lf = leaf(c)
+            if lf not in leaves:
+                leaves.append(lf)
+            prog.append(leaves.index(lf))
+        elif isinstance(c, Not):
+            emit(c.arg)
+            prog.append(A.F_NOT)
+        elif isinstance(c, (And, Or)):
+            emit(c.lhs)
+            emit(c.rhs)
+            prog.append(A.F_AND if isinstance(c, And) else A.F_OR)
+        else:
+            raise QueryMustRunOnCpu(f"unsupported HAVING condition {c!r}")
+
+    for i, c in enumerate(having):
+        emit(c)
+        if i:
+            prog.append(A.F_AND)
+    if len(leaves) > A.MAX_HAVING_LEAVES:
+        raise QueryMustRunOnCpu("more than %d HAVING comparisons" % A.MAX_HAVING_LEAVES)
+    if all(isinstance(c, Cmp) for c in having):
+        return Having(leaves, [])  # the plain conjunction (of the distinct comparisons: a repeated one changes nothing)
+    if len(prog) > A.MAX_FILTER_OPS:
+        raise QueryMustRunOnCpu("HAVING expression too long for the fixed kernel library (%d ops, at most %d)"
+                                % (len(prog), A.MAX_FILTER_OPS))
+    return Having(leaves, prog)
+
+
+def _names_target(e) -> bool:
+    """an expression or condition tree holds an ir.TargetRef"""
+    if isinstance(e, TargetRef):
+        return True
+    if isinstance(e, (BinOp, Cmp, And, Or)):
+        return _names_target(e.lhs) or _names_target(e.rhs)
+    if isinstance(e, (ExtractYear, Cast, Not)):
+        return _names_target(e.arg)
+    return False
+
+
+def _reject_target_refs_outside_having(q: QueryUnit):
+    from .ir import Proj
+    places = [("quals", c) for c in q.quals] + [("groupby", e) for e in q.groupby]
+    places += [("targets", t.arg if isinstance(t, Agg) else t.expr) for t in q.targets if isinstance(t, (Agg, Proj))]
+    places += [("joins", k) for j in q.joins for k in j.outer_keys]
+    for where, e in places:
+        if _names_target(e):
+            raise ValueError(f"ir.TargetRef names a target of the step's RESULT and is valid only inside QueryUnit.having; "
+                             f"found in {where}: {e!r}")
+
+
 def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
     from .ir import Proj
+    _reject_target_refs_outside_having(q)
     if q.limit is not None and q.limit < 0 or q.offset < 0:
         raise ValueError("limit and offset must not be negative")
     if q.targets and all(isinstance(t, Proj) for t in q.targets):
@@ -730,6 +874,8 @@ def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
             raise QueryMustRunOnCpu("projection targets with GROUP BY")
         if _has_sort_info(q):
             raise QueryMustRunOnCpu("ORDER BY / LIMIT / OFFSET on a projection: it has no dense device columns")
+        if q.having:
+            raise QueryMustRunOnCpu("HAVING on a step that is not a group-by: a projection has no dense device columns")
         return compile_projection(storage, q)
     if any(isinstance(t, Proj) for t in q.targets):
         raise QueryMustRunOnCpu("mixing projections and aggregates")
@@ -1054,11 +1200,13 @@ def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
         if kind == A.Q_NON_GROUPED:
             raise QueryMustRunOnCpu("ORDER BY / LIMIT / OFFSET on a non-grouped query: it has no dense device columns")
         order_by = resolve_order_by(out_cols, int(p.num_targets), q.order_by)
-    return CompiledPlan(plan=p, query=q, init_vals=np.array(init_vals, dtype=np.int64),
-                        slot_widths=slot_widths, input_cols=list(b.cols),
-                        inner_tables=[t.name for t in b.inner], join_infos=join_infos,
-                        out_cols=out_cols, key_types=key_types, buffer_bytes=buffer_bytes,
-                        key_ranges=key_ranges, order_by=order_by)
+    cp = CompiledPlan(plan=p, query=q, init_vals=np.array(init_vals, dtype=np.int64),
+                      slot_widths=slot_widths, input_cols=list(b.cols),
+                      inner_tables=[t.name for t in b.inner], join_infos=join_infos,
+                      out_cols=out_cols, key_types=key_types, buffer_bytes=buffer_bytes,
+                      key_ranges=key_ranges, order_by=order_by)
+    cp.having = resolve_having(cp, q.having)
+    return cp
 
 
 # ---------------------------------------------------------------------------------------------

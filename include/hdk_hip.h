@@ -649,6 +649,68 @@ int32_t hdk_hip_sort_columns(const int64_t* cols, uint64_t capacity, int32_t num
                              size_t workspace_bytes, int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * HAVING over dense result columns on the device: the rows on which a predicate is TRUE, compacted.
+ * Replaces, for a result whose columns sit in HBM, the reference's filter step over a temporary table (the previous
+ * step's ResultSet materialised as ColumnarResults), whose comparisons are DEF_CMP_NULLABLE*
+ * (omniscidb/QueryEngine/RuntimeFunctions.cpp:83-117) combined by logical_not / logical_and / logical_or (:355-384).
+ * Input: `num_cols` columns of `num_rows` 8-byte words, column t at cols + t * capacity, NULLs in band -- what
+ * hdk_hip_columnarize_result and hdk_hip_sort_columns write.
+ * Predicate: `num_leaves` (1..HDK_HIP_MAX_HAVING_LEAVES) comparisons and a postfix program `ops` over them of up to
+ * HDK_HIP_MAX_FILTER_OPS bytes in the encoding of hdk_hip_plan::filter_ops: a byte < HDK_F_AND pushes the value of
+ * leaves[byte] (TRUE / FALSE / NULL), HDK_F_AND and HDK_F_OR combine the two topmost values, HDK_F_NOT negates the
+ * topmost.  num_ops == 0: the plain conjunction of all leaves.  A row passes only when the result is TRUE; NULL and
+ * FALSE both drop it.
+ * Leaf: column lhs_col <cmp> column rhs_col (rhs_is_col) or the literal rhs_lit (an int64, or a double's bits with
+ * rhs_is_fp).  A side is NULL when it is nullable and its word EQUALS null_bits -- a bit compare, the rule of
+ * hdk_hip_order_entry; a literal is never NULL; a leaf with a NULL side is NULL.  With cmp_fp the sides are compared as
+ * doubles, an int64 side (is_fp == 0) converted with (double) as the reference's cast would; without it the words are
+ * compared as int64 and is_fp is not looked at.
+ * Doubles compare with the C operators, UNLIKE hdk_hip_sort_columns' order: -0.0 == +0.0 holds, and any comparison
+ * with a NaN is false except <> (HDK_CMP_NE), which is true.
+ * Output: column t at out_cols + t * out_capacity; passing rows keep their input order (stable).  *row_count (device)
+ * ALWAYS receives the true number of passing rows; rows at or beyond out_capacity are not written, and nothing outside
+ * [0, min(rows, out_capacity)) of an output column is touched.  out_cols == NULL: count only (perm_out is ignored).
+ * perm_out (device, may be NULL; out_capacity entries) receives the input row index of each output row.  The input is
+ * not modified, and no two of cols, out_cols, perm_out, row_count and workspace may overlap (a block the call does not
+ * touch -- out_cols and perm_out with out_capacity == 0 or in a count-only call -- has no bytes and overlaps nothing).
+ * `workspace`: hdk_hip_filter_columns_workspace_bytes(num_rows) bytes of device memory, 8-byte aligned (host arithmetic only: one pass
+ * bit per row and 4 bytes per tile of 4 096 rows, both rounded up to whole tiles, plus at most 512 bytes), or NULL -- the
+ * library then takes it from the stream's memory pool (hipMallocAsync), as its two siblings do.
+ * ASYNCHRONOUS on `stream`: three launches (count, scan, compact) ordered by the stream alone; the host never waits
+ * (as hdk_hip_columnarize_result, unlike hdk_hip_sort_columns).  Output and *row_count are complete when `stream` has
+ * drained.
+ * Errors, all found before any device is touched (HDK_HIP_ERR_INVALID_ARG with a message): a NULL cols / leaves /
+ * row_count, num_leaves outside 1..8, a column index outside [0, num_cols), a cmp outside hdk_hip_cmp, a malformed
+ * program (more than HDK_HIP_MAX_FILTER_OPS ops, an unknown byte, stack underflow, a leaf index >= num_leaves, a final
+ * stack depth other than 1), num_rows >= 2^32, num_rows > capacity, overlapping blocks, a workspace that is too small
+ * or not 8-byte aligned.
+ * num_rows == 0: *row_count = 0 is stored on the stream, nothing else is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define HDK_HIP_MAX_HAVING_LEAVES 8
+
+typedef struct hdk_hip_having_leaf {
+  int32_t lhs_col;        /* 0-based column = target index */
+  int32_t rhs_col;        /* with rhs_is_col */
+  uint8_t cmp;            /* hdk_hip_cmp */
+  uint8_t rhs_is_col;     /* 0: the right-hand side is rhs_lit */
+  uint8_t cmp_fp;         /* compare as doubles (a side is fp, or the literal is); else as int64 */
+  uint8_t lhs_is_fp;      /* the column's words are doubles */
+  uint8_t lhs_nullable;   /* 0: lhs_null_bits is an ordinary value */
+  uint8_t rhs_is_fp;      /* the column's words, or rhs_lit, are a double('s bits) */
+  uint8_t rhs_nullable;   /* a column only: a literal is never NULL */
+  uint8_t pad_;
+  int64_t lhs_null_bits;  /* the column's in-band NULL as the dense column holds it */
+  int64_t rhs_null_bits;
+  int64_t rhs_lit;
+} hdk_hip_having_leaf;
+
+size_t hdk_hip_filter_columns_workspace_bytes(uint64_t num_rows);
+int32_t hdk_hip_filter_columns(const int64_t* cols, uint64_t capacity, int32_t num_cols, uint64_t num_rows,
+                               const hdk_hip_having_leaf* leaves, int32_t num_leaves, const uint8_t* ops, int32_t num_ops,
+                               int64_t* out_cols, uint64_t out_capacity, uint64_t* row_count, uint32_t* perm_out,
+                               void* workspace, size_t workspace_bytes, int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Environment switches (MI355X addition; no reference counterpart: the reference's knobs are Config fields,
  * Shared/Config.h).  libhdk_hip.so reads its HDK_HIP_* variables (tests and A/B measurements, none needed
  * in production) ONCE per process, at the first launch that asks for one -- never per launch, so a host that calls
