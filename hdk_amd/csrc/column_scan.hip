@@ -1,0 +1,68 @@
+// column_scan.hip -- the one-block exclusive scan of per-tile counters that the result stages share (result_columns.hip,
+// sort_columns.hip, filter_columns.hip): count -> this scan -> compact / scatter, ordered by the stream alone.
+#include "column_primitives.h"
+#include "host_common.h"
+
+namespace hdk {
+
+constexpr int kScanBlock = 1024;
+
+// counts[0 .. n) -> exclusive offsets in place, counts[n] = the total, *total_out = the total when asked for.  The total
+// counts rows or entries of one call and stays below 2^32.  Slot [n] lies inside every caller's counter region: the
+// result and filter workspaces hold ntiles + 1 counters (hdk_hip_result_columns_workspace_bytes, fc_counts_bytes) and
+// are scanned with n = ntiles; the sort workspace holds 256 * tiles(num_rows) + 1 (sc_carve) and is scanned with
+// n = 256 * mtiles, mtiles <= tiles(num_rows), or with n = tiles(num_rows) >= 1 by the top-N selection.
+// PER counters per thread and trip: a trip covers kScanBlock * PER counters, the carry runs from trip to trip.
+template <int PER>
+__global__ __launch_bounds__(kScanBlock) void hdk_counts_scan(uint32_t* __restrict__ counts, uint32_t n,
+                                                               uint64_t* __restrict__ total_out) {
+  __shared__ uint32_t s_wave[kScanBlock / kWave];
+  const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < n; base += kScanBlock * PER) {
+    const uint32_t i0 = base + threadIdx.x * PER;
+    uint32_t v[PER];
+    uint32_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      v[k] = i0 + k < n ? counts[i0 + k] : 0;
+      mine += v[k];
+    }
+    const uint32_t incl = wave_inclusive_sum(mine, lane);
+    if (lane == kWave - 1) {
+      s_wave[wave] = incl;
+    }
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kScanBlock / kWave; ++w) {
+      const uint32_t c = s_wave[w];
+      before += static_cast<uint32_t>(w) < wave ? c : 0;
+      total += c;
+    }
+    uint32_t run = carry + before + incl - mine;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+      if (i0 + k < n) counts[i0 + k] = run;
+      run += v[k];
+    }
+    carry += total;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    counts[n] = carry;
+    if (total_out) {
+      *total_out = carry;
+    }
+  }
+}
+
+void launch_counts_scan(uint32_t* counts, uint32_t n, ScanPer per, uint64_t* total_out, hipStream_t s) {
+  if (per == SCAN_PER_16) {
+    hipLaunchKernelGGL(hdk_counts_scan<16>, dim3(1), dim3(kScanBlock), 0, s, counts, n, total_out);
+  } else {
+    hipLaunchKernelGGL(hdk_counts_scan<4>, dim3(1), dim3(kScanBlock), 0, s, counts, n, total_out);
+  }
+}
+
+}  // namespace hdk

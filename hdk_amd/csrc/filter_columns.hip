@@ -10,7 +10,7 @@
 //                       (bit j of a lane's mask = its j-th row of the tile), the postfix program over the masks -- no
 //                       per-row control flow --, one pass bit per row (a 64-bit ballot word per wave-row, which lands at
 //                       bits[row / 64]) and the tile's count -> workspace
-//   hdk_filter_scan     one block: exclusive scan of the tile counts in place, the total -> *row_count
+//   hdk_counts_scan<4>  one block (column_scan.hip): exclusive scan of the tile counts in place, the total -> *row_count
 //   hdk_filter_compact  per tile: a tile without a passing row is skipped unread; otherwise the tile's 64 ballot words,
 //                       rank = tile offset + words before + mbcnt, and every column loaded only for passing rows and
 //                       written at column + rank
@@ -20,20 +20,19 @@
 // for its leaf.  Traffic: count 8n per column read + n/8; compact n/8 + 16 bytes per column and passing row.
 #include <string.h>
 
-#include "device_common.h"
+#include "column_primitives.h"
 #include "host_common.h"
 
 namespace hdk {
 
-constexpr int kFcBlock = 256;
+constexpr int kFcBlock = kTileBlock;
 constexpr int kFcItems = 16;  // rows per thread and tile
 constexpr uint32_t kFcTile = kFcBlock * kFcItems;
 constexpr int kFcWaves = kFcBlock / kWave;
 constexpr int kFcWords = kFcItems * kFcWaves;  // ballot words of a tile, in row order: word j * kFcWaves + wave
 static_assert(kFcWords == kWave, "one wave scans the ballot words of a tile");
 static_assert(kFcItems <= 32, "a lane's rows are one 32-bit mask");
-constexpr int kFcScanBlock = 1024;
-constexpr int kFcScanPer = 4;  // tile counts per thread and trip
+constexpr ScanPer kFcScanPer = SCAN_PER_4;  // tile counts per thread and trip of the scan
 constexpr int kFcStack = HDK_HIP_MAX_HAVING_LEAVES;  // 16 ops hold at most 8 pushes beside their 7 binary operators
 
 enum FcFlag : uint32_t {
@@ -59,13 +58,7 @@ struct FcDesc {
 };
 
 // the columns are read once per pass: every load is non-temporal
-HDK_DEV int64_t fc_load(const int64_t* p) {
-  return __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) int64_t*>(reinterpret_cast<uintptr_t>(p)));
-}
-
-HDK_DEV uint32_t fc_lane_rank(uint64_t mask) {  // set bits of `mask` below this lane
-  return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-}
+HDK_DEV int64_t fc_load(const int64_t* p) { return nt_load<int64_t>(p, 0); }
 
 HDK_DEV uint64_t fc_shfl64(uint64_t v, uint32_t src) {
   const uint32_t lo = __shfl(static_cast<uint32_t>(v), static_cast<int>(src), kWave);
@@ -221,66 +214,7 @@ __global__ __launch_bounds__(kFcBlock) void hdk_filter_count(const int64_t* __re
       }
       cnt += static_cast<uint32_t>(__popcll(mask));
     }
-    if (lane == 0) {
-      s_wave[wave] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t sum = 0;
-#pragma unroll
-      for (int w = 0; w < kFcWaves; ++w) {
-        sum += s_wave[w];
-      }
-      tile_counts[tile] = sum;
-    }
-    __syncthreads();
-  }
-}
-
-// counts[0 .. ntiles) -> exclusive offsets in place, counts[ntiles] = *row_count = the total (<= n < 2^32)
-__global__ __launch_bounds__(kFcScanBlock) void hdk_filter_scan(uint32_t* __restrict__ counts, uint32_t ntiles,
-                                                                uint64_t* __restrict__ row_count) {
-  __shared__ uint32_t s_wave[kFcScanBlock / kWave];
-  const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < ntiles; base += kFcScanBlock * kFcScanPer) {
-    const uint32_t i0 = base + threadIdx.x * kFcScanPer;
-    uint32_t v[kFcScanPer];
-    uint32_t mine = 0;
-#pragma unroll
-    for (int k = 0; k < kFcScanPer; ++k) {
-      v[k] = i0 + k < ntiles ? counts[i0 + k] : 0;
-      mine += v[k];
-    }
-    uint32_t incl = mine;
-#pragma unroll
-    for (int s = 1; s < kWave; s <<= 1) {
-      const uint32_t up = __shfl_up(incl, s, kWave);
-      if (lane >= static_cast<uint32_t>(s)) incl += up;
-    }
-    if (lane == kWave - 1) {
-      s_wave[wave] = incl;
-    }
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kFcScanBlock / kWave; ++w) {
-      const uint32_t c = s_wave[w];
-      before += static_cast<uint32_t>(w) < wave ? c : 0;
-      total += c;
-    }
-    uint32_t run = carry + before + incl - mine;
-#pragma unroll
-    for (int k = 0; k < kFcScanPer; ++k) {
-      if (i0 + k < ntiles) counts[i0 + k] = run;
-      run += v[k];
-    }
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    counts[ntiles] = carry;
-    *row_count = carry;
+    block_store_tile_count(s_wave, cnt, tile_counts + tile);
   }
 }
 
@@ -298,13 +232,7 @@ __global__ __launch_bounds__(kFcBlock) void hdk_filter_compact(const int64_t* __
     }
     const uint64_t word = bits[static_cast<uint64_t>(tile) * kFcWords + lane];
     const uint32_t c = static_cast<uint32_t>(__popcll(word));
-    uint32_t incl = c;
-#pragma unroll
-    for (int s = 1; s < kWave; s <<= 1) {
-      const uint32_t up = __shfl_up(incl, s, kWave);
-      if (lane >= static_cast<uint32_t>(s)) incl += up;
-    }
-    const uint32_t excl = incl - c;
+    const uint32_t excl = wave_inclusive_sum(c, lane) - c;
     const uint64_t r0 = static_cast<uint64_t>(tile) * kFcTile + threadIdx.x;
     uint32_t flags = 0;
     uint64_t rank[kFcItems];
@@ -313,7 +241,7 @@ __global__ __launch_bounds__(kFcBlock) void hdk_filter_compact(const int64_t* __
       const uint32_t w = static_cast<uint32_t>(j) * kFcWaves + wave;
       const uint64_t mask = fc_shfl64(word, w);
       const uint32_t before = __shfl(excl, static_cast<int>(w), kWave);
-      rank[j] = static_cast<uint64_t>(first) + before + fc_lane_rank(mask);
+      rank[j] = static_cast<uint64_t>(first) + before + lane_rank(mask);
       const bool f = ((mask >> lane) & 1u) && rank[j] < out_capacity;
       flags |= static_cast<uint32_t>(f) << j;
     }
@@ -347,7 +275,7 @@ __global__ __launch_bounds__(kFcBlock) void hdk_filter_compact(const int64_t* __
 }
 
 static size_t fc_tiles(uint64_t num_rows) { return static_cast<size_t>((num_rows + kFcTile - 1) / kFcTile); }
-static size_t fc_counts_bytes(size_t ntiles) { return ((ntiles + 1) * sizeof(uint32_t) + 255) & ~static_cast<size_t>(255); }
+static size_t fc_counts_bytes(size_t ntiles) { return align256((ntiles + 1) * sizeof(uint32_t)); }
 
 // the program is well formed: no underflow, no leaf beyond `num_leaves`, one value left
 static const char* fc_check_program(const uint8_t* ops, int32_t num_ops, int32_t num_leaves) {
@@ -415,24 +343,15 @@ extern "C" int32_t hdk_hip_filter_columns(const int64_t* cols, uint64_t capacity
     // every block the call reads or writes; a block nothing is written to or read from (out_capacity == 0, count only)
     // has no bytes and overlaps nothing
     const bool writes = out_cols && out_capacity;
-    const struct {
-      const char* name;
-      uintptr_t at;
-      uint64_t bytes;
-    } blk[] = {
+    const MemBlock blk[] = {
         {"cols", reinterpret_cast<uintptr_t>(cols), static_cast<uint64_t>(num_cols) * capacity * 8},
         {"out_cols", reinterpret_cast<uintptr_t>(out_cols), writes ? static_cast<uint64_t>(num_cols) * out_capacity * 8 : 0},
         {"perm_out", reinterpret_cast<uintptr_t>(perm_out), writes && perm_out ? out_capacity * 4 : 0},
         {"row_count", reinterpret_cast<uintptr_t>(row_count), 8},
         {"workspace", reinterpret_cast<uintptr_t>(workspace), workspace ? static_cast<uint64_t>(need) : 0},
     };
-    constexpr int kBlocks = sizeof(blk) / sizeof(blk[0]);
-    for (int i = 0; i < kBlocks; ++i) {
-      for (int k = i + 1; k < kBlocks; ++k) {
-        HDK_REQUIRE(!blk[i].bytes || !blk[k].bytes || blk[i].at + blk[i].bytes <= blk[k].at || blk[k].at + blk[k].bytes <= blk[i].at,
-                    "hdk_hip_filter_columns: %s overlaps %s", blk[k].name, blk[i].name);
-      }
-    }
+    const int32_t bad = require_disjoint("hdk_hip_filter_columns", blk, sizeof(blk) / sizeof(blk[0]));
+    if (bad) return bad;
   }
   hipStream_t s;
   int32_t st = device_enter(device_id, stream, &s);
@@ -486,19 +405,14 @@ extern "C" int32_t hdk_hip_filter_columns(const int64_t* cols, uint64_t capacity
   }
 
   AsyncScratch mem(s);
-  if (!workspace) {
-    HDK_HIP_CHECK(hipMallocAsync(&mem.p, need, s));
-    workspace = mem.p;
-  }
+  st = acquire_workspace(mem, &workspace, need);
+  if (st) return st;
   const uint32_t ntiles = static_cast<uint32_t>(fc_tiles(num_rows));
   uint32_t* tiles = static_cast<uint32_t*>(workspace);
   uint64_t* bits = reinterpret_cast<uint64_t*>(static_cast<int8_t*>(workspace) + fc_counts_bytes(ntiles));
-  const hdk_hip_device_properties* props = device_props(device_id);
-  size_t blocks = static_cast<size_t>(props->num_cu) * 8;
-  if (blocks > ntiles) blocks = ntiles;
-  const dim3 grid(static_cast<unsigned>(blocks)), block(kFcBlock);
+  const dim3 grid(persistent_grid(device_props(device_id), ntiles)), block(kFcBlock);
   hipLaunchKernelGGL(hdk_filter_count, grid, block, 0, s, cols, capacity, static_cast<uint32_t>(num_rows), d, ntiles, tiles, bits);
-  hipLaunchKernelGGL(hdk_filter_scan, dim3(1), dim3(kFcScanBlock), 0, s, tiles, ntiles, row_count);
+  launch_counts_scan(tiles, ntiles, kFcScanPer, row_count, s);
   if (out_cols && out_capacity) {
     hipLaunchKernelGGL(hdk_filter_compact, grid, block, 0, s, cols, capacity, static_cast<uint32_t>(num_cols), ntiles, tiles, bits,
                        out_cols, out_capacity, perm_out);

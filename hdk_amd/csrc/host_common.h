@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/hdk_hip.h"
@@ -16,6 +17,10 @@ int32_t device_enter(int32_t device_id, void* stream, hipStream_t* out);
 const hdk_hip_device_properties* device_props(int32_t device_id);
 // the device's interrupt word (device memory, 0 = run): polled by launches with HDK_HIP_LAUNCH_CHECK_INTERRUPT
 const int32_t* device_interrupt_word(int32_t device_id);
+// column_scan.hip: one block scans counts[0 .. n) exclusively in place, `per` counters per thread and trip;
+// counts[n] = the total, and *total_out too when it is not NULL
+enum ScanPer { SCAN_PER_4 = 4, SCAN_PER_16 = 16 };
+void launch_counts_scan(uint32_t* counts, uint32_t n, ScanPer per, uint64_t* total_out, hipStream_t s);
 // init_groups.hip: the row-wise fill for a buffer named by GROUPBY_BUF[0] (device memory)
 int32_t launch_init_row_wise_indirect(int64_t* const* groupby_buf, const int64_t* init_vals, uint32_t entry_count,
                                       uint32_t key_count, uint32_t key_width, uint32_t row_size_quad, int keyless,
@@ -50,5 +55,40 @@ struct AsyncScratch {
     if (p) (void)hipFreeAsync(p, s);
   }
 };
+
+constexpr size_t align256(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
+
+// blocks of a persistent grid: eight per compute unit, and no more than there is work
+inline unsigned persistent_grid(const hdk_hip_device_properties* props, uint64_t work_items) {
+  const uint64_t cap = static_cast<uint64_t>(props->num_cu) * 8;
+  return static_cast<unsigned>(work_items < cap ? work_items : cap);
+}
+
+// the caller's workspace, or (when it gave none) `need` stream-ordered bytes that `mem` hands back
+inline int32_t acquire_workspace(AsyncScratch& mem, void** workspace, size_t need) {
+  if (!*workspace) {
+    HDK_HIP_CHECK(hipMallocAsync(&mem.p, need, mem.s));
+    *workspace = mem.p;
+  }
+  return HDK_HIP_OK;
+}
+
+struct MemBlock {
+  const char* name;
+  uintptr_t at;
+  uint64_t bytes;
+};
+
+// no two of the blocks share a byte; a block of zero bytes overlaps nothing
+inline int32_t require_disjoint(const char* fn, const MemBlock* blocks, int n) {
+  for (int i = 0; i < n; ++i) {
+    for (int k = i + 1; k < n; ++k) {
+      const MemBlock &a = blocks[i], &b = blocks[k];
+      HDK_REQUIRE(!a.bytes || !b.bytes || a.at + a.bytes <= b.at || b.at + b.bytes <= a.at, "%s: %s overlaps %s", fn, b.name,
+                  a.name);
+    }
+  }
+  return HDK_HIP_OK;
+}
 
 }  // namespace hdk

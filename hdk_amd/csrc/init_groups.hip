@@ -51,10 +51,8 @@ int32_t launch_init_row_wise_indirect(int64_t* const* groupby_buf, const int64_t
   if (total_quads == 0) {
     return HDK_HIP_OK;
   }
-  uint64_t blocks = (total_quads + kInitBlock - 1) / kInitBlock;
-  const uint64_t cap = static_cast<uint64_t>(props->num_cu) * 8;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(k_init_row_wise_indirect, dim3(static_cast<unsigned>(blocks)), dim3(kInitBlock), 0, s, groupby_buf,
+  const unsigned blocks = persistent_grid(props, (total_quads + kInitBlock - 1) / kInitBlock);
+  hipLaunchKernelGGL(k_init_row_wise_indirect, dim3(blocks), dim3(kInitBlock), 0, s, groupby_buf,
                      init_vals, total_quads, row_size_quad, key_count, key_width, keyless);
   HDK_HIP_CHECK(hipGetLastError());
   return HDK_HIP_OK;
@@ -154,10 +152,8 @@ extern "C" int32_t hdk_hip_init_group_by_buffer(int64_t* groups_buffer, const in
     return HDK_HIP_OK;
   }
   const hdk_hip_device_properties* props = device_props(device_id);
-  uint64_t blocks = (total_quads + kInitBlock - 1) / kInitBlock;
-  const uint64_t cap = static_cast<uint64_t>(props->num_cu) * 8;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(k_init_row_wise, dim3(static_cast<unsigned>(blocks)), dim3(kInitBlock), 0, s,
+  const unsigned blocks = persistent_grid(props, (total_quads + kInitBlock - 1) / kInitBlock);
+  hipLaunchKernelGGL(k_init_row_wise, dim3(blocks), dim3(kInitBlock), 0, s,
                      groups_buffer, init_vals, total_quads, row_size_quad, key_count, key_width,
                      keyless ? 1 : 0);
   HDK_HIP_CHECK(hipGetLastError());
@@ -180,10 +176,8 @@ extern "C" int32_t hdk_hip_init_columnar_group_by_buffer(
     return HDK_HIP_OK;
   }
   const hdk_hip_device_properties* props = device_props(device_id);
-  uint64_t blocks = (n + kInitBlock - 1) / kInitBlock;
-  const uint64_t cap = static_cast<uint64_t>(props->num_cu) * 8;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(k_init_columnar, dim3(static_cast<unsigned>(blocks)), dim3(kInitBlock), 0, s,
+  const unsigned blocks = persistent_grid(props, (n + kInitBlock - 1) / kInitBlock);
+  hipLaunchKernelGGL(k_init_columnar, dim3(blocks), dim3(kInitBlock), 0, s,
                      reinterpret_cast<int8_t*>(groups_buffer), init_vals, groups_buffer_entry_count,
                      key_count, agg_col_count, col_sizes, need_padding ? 1 : 0, keyless ? 1 : 0,
                      static_cast<int>(key_size));

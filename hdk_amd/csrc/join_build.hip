@@ -11,7 +11,7 @@
 // (JoinColumnIterator.h:30-100); here each chunk is swept by the whole grid with coalesced loads,
 // and the scan is a hand-written 3-kernel block scan instead of thrust::inclusive_scan.
 #include <cstring>
-#include "device_common.h"
+#include "column_primitives.h"
 #include "host_common.h"
 #include "switches.h"
 
@@ -131,13 +131,7 @@ HDK_DEV int32_t block_exclusive_scan(int32_t v, int32_t* total) {
   __shared__ int32_t wave_sums[kJoinBlock / kWave];
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
-  int32_t incl = v;
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int32_t n = __shfl_up(incl, d, kWave);
-    if (lane >= d) {
-      incl += n;
-    }
-  }
+  const int32_t incl = wave_inclusive_sum(v, lane);
   if (lane == kWave - 1) {
     wave_sums[wave] = incl;
   }
@@ -228,12 +222,8 @@ __global__ __launch_bounds__(kJoinBlock) void k_set_valid_pos(int32_t* __restric
 }
 
 static unsigned grid_for(size_t n, int32_t device_id) {
-  const hdk_hip_device_properties* props = device_props(device_id);
-  size_t blocks = (n + kJoinBlock - 1) / kJoinBlock;
-  const size_t cap = static_cast<size_t>(props->num_cu) * 8;
-  if (blocks > cap) blocks = cap;
-  if (blocks == 0) blocks = 1;
-  return static_cast<unsigned>(blocks);
+  const unsigned blocks = persistent_grid(device_props(device_id), (n + kJoinBlock - 1) / kJoinBlock);
+  return blocks ? blocks : 1;
 }
 
 static int32_t inclusive_scan_inplace(int32_t* data, int64_t n, hipStream_t s) {
@@ -582,8 +572,6 @@ struct PbLayout {
   size_t off_fill1, off_fill2, off_t1, off_t2, cursor_bytes, total;
 };
 
-static size_t pb_up(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
-
 // false: this table is not one for the partitioned build (no rows, more row ids or slots than 32 bits address)
 static bool pb_geometry(PbArgs* a, PbLayout* l, int64_t rows, int64_t entries, int np) {
   if (rows <= 0 || entries <= 0 || rows > INT32_MAX || entries > INT32_MAX || np < 0 || np > kPbMaxPayload) return false;
@@ -611,11 +599,11 @@ static bool pb_geometry(PbArgs* a, PbLayout* l, int64_t rows, int64_t entries, i
   a->cap2 = 1ull << a->slice_log2;
   if (a->cap1 > 0xFFFFFFF0ull) return false;
   l->off_fill1 = 256;  // [0]: the flag word
-  l->off_fill2 = l->off_fill1 + pb_up(nsub * kPbCursorStride * 4);
-  l->cursor_bytes = l->off_fill2 + (a->two_level ? pb_up(static_cast<size_t>(a->nslices) * kPbCursor2Stride * 4) : 0);
+  l->off_fill2 = l->off_fill1 + align256(nsub * kPbCursorStride * 4);
+  l->cursor_bytes = l->off_fill2 + (a->two_level ? align256(static_cast<size_t>(a->nslices) * kPbCursor2Stride * 4) : 0);
   l->off_t1 = l->cursor_bytes;
-  l->off_t2 = l->off_t1 + pb_up(nsub * a->cap1 * tw * 8);
-  l->total = l->off_t2 + (a->two_level ? pb_up(static_cast<size_t>(a->nslices) * a->cap2 * tw * 8) : 0);
+  l->off_t2 = l->off_t1 + align256(nsub * a->cap1 * tw * 8);
+  l->total = l->off_t2 + (a->two_level ? align256(static_cast<size_t>(a->nslices) * a->cap2 * tw * 8) : 0);
   if (l->total > (static_cast<size_t>(16) << 30)) return false;  // (never starve the stream pool: the atomic build needs no scratch)
   return true;
 }

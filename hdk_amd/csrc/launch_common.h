@@ -15,7 +15,7 @@ constexpr uint64_t kLdsWordBudget = 4096;
 constexpr uint64_t kLdsMaxTableWords = 7680;
 // head of a launch's workspace: [plan copy | LaunchWatch (watch.h)], padded to 256 bytes
 constexpr size_t kWatchOffset = (sizeof(hdk_hip_plan) + 15) & ~static_cast<size_t>(15);
-constexpr size_t kPlanRegionBytes = (kWatchOffset + 16 + 255) & ~static_cast<size_t>(255);
+constexpr size_t kPlanRegionBytes = align256(kWatchOffset + 16);
 
 struct LaunchShape {
   Strategy strategy;

@@ -483,7 +483,7 @@ static int32_t run_partition(const hdk_hip_plan* plan, const int64_t* buf, uint3
   SlotInit init;
   fill_slot_init(plan, init_vals, &init);
   AsyncScratch mem(s);  // [plan | cursors]
-  constexpr size_t kPlanBytes = (sizeof(hdk_hip_plan) + 255) & ~size_t(255);
+  constexpr size_t kPlanBytes = align256(sizeof(hdk_hip_plan));
   HDK_HIP_CHECK(hipMallocAsync(&mem.p, kPlanBytes + kMaxOwners * sizeof(uint32_t), s));
   int8_t* scratch = static_cast<int8_t*>(mem.p);
   hdk_hip_plan* d_plan = reinterpret_cast<hdk_hip_plan*>(scratch);
@@ -491,16 +491,14 @@ static int32_t run_partition(const hdk_hip_plan* plan, const int64_t* buf, uint3
   HDK_HIP_CHECK(hipMemcpyAsync(d_plan, plan, sizeof(hdk_hip_plan), hipMemcpyHostToDevice, s));
   HDK_HIP_CHECK(hipMemsetAsync(cursors, 0, kMaxOwners * sizeof(uint32_t), s));
   const hdk_hip_device_properties* props = device_props(device_id);
-  size_t blocks = (static_cast<size_t>(entry_count) + kRedBlock * kPartT - 1) / (kRedBlock * kPartT);
-  const size_t cap = static_cast<size_t>(props->num_cu) * 8;
-  if (blocks > cap) blocks = cap;
+  unsigned blocks = persistent_grid(props, (static_cast<size_t>(entry_count) + kRedBlock * kPartT - 1) / (kRedBlock * kPartT));
   if (blocks == 0) blocks = 1;
   const bool k32 = !plan->output_columnar && plan->key_width == 4;
   if (k32) {
-    hipLaunchKernelGGL((k_partition_baseline<int32_t, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(kRedBlock), 0, s,
+    hipLaunchKernelGGL((k_partition_baseline<int32_t, MODE>), dim3(blocks), dim3(kRedBlock), 0, s,
                        d_plan, buf, entry_count, static_cast<uint32_t>(num_owners), init, cursors, segs);
   } else {
-    hipLaunchKernelGGL((k_partition_baseline<int64_t, MODE>), dim3(static_cast<unsigned>(blocks)), dim3(kRedBlock), 0, s,
+    hipLaunchKernelGGL((k_partition_baseline<int64_t, MODE>), dim3(blocks), dim3(kRedBlock), 0, s,
                        d_plan, buf, entry_count, static_cast<uint32_t>(num_owners), init, cursors, segs);
   }
   HDK_HIP_CHECK(hipGetLastError());
@@ -569,14 +567,12 @@ extern "C" int32_t hdk_hip_reduce_buffers(const hdk_hip_plan* plan, int64_t* thi
     HDK_REQUIRE(dev_error, "dev_error is NULL");
     for (int i = 0; i < num_that; ++i) {
       if (that_entry_counts[i] == 0) continue;
-      size_t blocks = (static_cast<size_t>(that_entry_counts[i]) + kRedBlock - 1) / kRedBlock;
-      const size_t cap = static_cast<size_t>(props->num_cu) * 8;
-      if (blocks > cap) blocks = cap;
+      const unsigned blocks = persistent_grid(props, (static_cast<size_t>(that_entry_counts[i]) + kRedBlock - 1) / kRedBlock);
       if (plan->key_width == 4) {
-        hipLaunchKernelGGL(k_reduce_baseline<int32_t>, dim3(static_cast<unsigned>(blocks)), dim3(kRedBlock), 0, s,
+        hipLaunchKernelGGL(k_reduce_baseline<int32_t>, dim3(blocks), dim3(kRedBlock), 0, s,
                            d_plan, this_buf, this_entry_count, that_bufs[i], that_entry_counts[i], init, dev_error);
       } else {
-        hipLaunchKernelGGL(k_reduce_baseline<int64_t>, dim3(static_cast<unsigned>(blocks)), dim3(kRedBlock), 0, s,
+        hipLaunchKernelGGL(k_reduce_baseline<int64_t>, dim3(blocks), dim3(kRedBlock), 0, s,
                            d_plan, this_buf, this_entry_count, that_bufs[i], that_entry_counts[i], init, dev_error);
       }
     }

@@ -9,7 +9,7 @@
 //
 // Three launches on one stream, ordered by nothing but the stream (no block ever waits for another block):
 //   hdk_result_count    persistent grid over tiles of kRcTile entries: non-empty entries per tile -> workspace
-//   hdk_result_scan     one block: exclusive scan of the tile counts in place, the total -> *row_count
+//   hdk_counts_scan<4>  one block (column_scan.hip): exclusive scan of the tile counts in place, the total -> *row_count
 //   hdk_result_compact  per tile: flags again, rank = tile offset + ballot/mbcnt rank, every column written at its rank;
 //                       tiles without a group are skipped unread (a sparse perfect-hash table costs one pass, not two)
 // The host decodes the plan once into a POD (RcDesc) that travels as a kernel argument: the entry loops read it from
@@ -17,20 +17,19 @@
 // key column (or the keyless slot column) plus the table plus the output.
 #include <string.h>
 
-#include "device_common.h"
+#include "column_primitives.h"
 #include "group_buffer.h"
 #include "host_common.h"
 
 namespace hdk {
 
-constexpr int kRcBlock = 256;
+constexpr int kRcBlock = kTileBlock;
 constexpr int kRcItems = 16;  // entries per thread and tile
 constexpr uint32_t kRcTile = kRcBlock * kRcItems;
 constexpr int kRcWaves = kRcBlock / kWave;
 constexpr int kRcParts = kRcItems * kRcWaves;  // (item, wave) partial counts of a tile, in entry order
 static_assert(kRcParts == kWave, "one wave scans the partial counts of a tile");
-constexpr int kRcScanBlock = 1024;
-constexpr int kRcScanPer = 4;  // tile counts per thread and trip
+constexpr ScanPer kRcScanPer = SCAN_PER_4;  // tile counts per thread and trip of the scan
 
 enum RcOp : uint32_t {
   RC_COPY = 0,            // the slot (or key), sign-extended; doubles keep their bits
@@ -56,23 +55,17 @@ struct RcDesc {
   RcCol col[HDK_HIP_MAX_TARGETS];
 };
 
-// the table is read once per pass and is larger than the last-level cache: every load is non-temporal
-template <typename T>
-HDK_DEV T rc_load(const int8_t* base, size_t off) {
-  return __builtin_nontemporal_load(
-      reinterpret_cast<const __attribute__((address_space(1))) T*>(reinterpret_cast<uintptr_t>(base + off)));
-}
-
+// the table is read once per pass and is larger than the last-level cache: every load is non-temporal (nt_load)
 HDK_DEV int64_t rc_load_sext(const int8_t* base, size_t off, uint32_t width) {
   switch (width) {
     case 1:
-      return rc_load<int8_t>(base, off);
+      return nt_load<int8_t>(base, off);
     case 2:
-      return rc_load<int16_t>(base, off);
+      return nt_load<int16_t>(base, off);
     case 4:
-      return rc_load<int32_t>(base, off);
+      return nt_load<int32_t>(base, off);
     default:
-      return rc_load<int64_t>(base, off);
+      return nt_load<int64_t>(base, off);
   }
 }
 
@@ -103,10 +96,6 @@ HDK_DEV int64_t rc_value(uint32_t op, int64_t a, int64_t b) {
   return double_to_bits(dividend / static_cast<double>(b));
 }
 
-HDK_DEV uint32_t lane_rank(uint64_t mask) {  // set bits of `mask` below this lane
-  return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-}
-
 // Entry e of a tile belongs to thread e % kRcBlock, item e / kRcBlock: consecutive lanes read consecutive entries.
 // (tile * kRcTile + 4095 never exceeds 2^32 - 1: tile < ceil(entry_count / kRcTile), entry_count < 2^32.)
 template <bool ROW16>
@@ -114,7 +103,6 @@ __global__ __launch_bounds__(kRcBlock) void hdk_result_count(const int8_t* __res
                                                               EmptyProbe probe, uint32_t ntiles,
                                                               uint32_t* __restrict__ tile_counts) {
   __shared__ uint32_t s_wave[kRcWaves];
-  const uint32_t wave = threadIdx.x / kWave;
   for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const uint32_t e0 = tile * kRcTile + threadIdx.x;
     int64_t word[kRcItems];
@@ -124,7 +112,7 @@ __global__ __launch_bounds__(kRcBlock) void hdk_result_count(const int8_t* __res
       const uint32_t e = e0 + static_cast<uint32_t>(j) * kRcBlock;
       const size_t ec = e < entry_count ? e : entry_count - 1;
       if (ROW16) {
-        word[j] = row16_word(rc_load<bf_i64x2>(buf, ec * 16), static_cast<uint32_t>(probe.base), probe.width);
+        word[j] = row16_word(nt_load<bf_i64x2>(buf, ec * 16), static_cast<uint32_t>(probe.base), probe.width);
       } else {
         word[j] = rc_load_sext(buf, probe.base + ec * probe.stride, probe.width);
       }
@@ -135,66 +123,7 @@ __global__ __launch_bounds__(kRcBlock) void hdk_result_count(const int8_t* __res
       const uint32_t e = e0 + static_cast<uint32_t>(j) * kRcBlock;
       n += static_cast<uint32_t>(__popcll(__builtin_amdgcn_ballot_w64(e < entry_count && word[j] != probe.empty)));
     }
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-      s_wave[wave] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t sum = 0;
-#pragma unroll
-      for (int w = 0; w < kRcWaves; ++w) {
-        sum += s_wave[w];
-      }
-      tile_counts[tile] = sum;
-    }
-    __syncthreads();
-  }
-}
-
-// counts[0 .. ntiles) -> exclusive offsets in place, counts[ntiles] = *row_count = the total (<= entry_count < 2^32)
-__global__ __launch_bounds__(kRcScanBlock) void hdk_result_scan(uint32_t* __restrict__ counts, uint32_t ntiles,
-                                                                uint64_t* __restrict__ row_count) {
-  __shared__ uint32_t s_wave[kRcScanBlock / kWave];
-  const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < ntiles; base += kRcScanBlock * kRcScanPer) {
-    const uint32_t i0 = base + threadIdx.x * kRcScanPer;
-    uint32_t v[kRcScanPer];
-    uint32_t mine = 0;
-#pragma unroll
-    for (int k = 0; k < kRcScanPer; ++k) {
-      v[k] = i0 + k < ntiles ? counts[i0 + k] : 0;
-      mine += v[k];
-    }
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, kWave);
-      if (lane >= static_cast<uint32_t>(d)) incl += up;
-    }
-    if (lane == kWave - 1) {
-      s_wave[wave] = incl;
-    }
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kRcScanBlock / kWave; ++w) {
-      const uint32_t c = s_wave[w];
-      before += static_cast<uint32_t>(w) < wave ? c : 0;
-      total += c;
-    }
-    uint32_t run = carry + before + incl - mine;
-#pragma unroll
-    for (int k = 0; k < kRcScanPer; ++k) {
-      if (i0 + k < ntiles) counts[i0 + k] = run;
-      run += v[k];
-    }
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    counts[ntiles] = carry;
-    *row_count = carry;
+    block_store_tile_count(s_wave, n, tile_counts + tile);
   }
 }
 
@@ -219,7 +148,7 @@ __global__ __launch_bounds__(kRcBlock) void hdk_result_compact(const int8_t* __r
       const uint32_t e = e0 + static_cast<uint32_t>(j) * kRcBlock;
       const size_t ec = e < entry_count ? e : entry_count - 1;
       if (ROW16) {
-        row[j] = rc_load<bf_i64x2>(buf, ec * 16);
+        row[j] = nt_load<bf_i64x2>(buf, ec * 16);
         word[j] = row16_word(row[j], static_cast<uint32_t>(d.probe.base), d.probe.width);
       } else {
         word[j] = rc_load_sext(buf, d.probe.base + ec * d.probe.stride, d.probe.width);
@@ -239,13 +168,7 @@ __global__ __launch_bounds__(kRcBlock) void hdk_result_compact(const int8_t* __r
     __syncthreads();
     if (wave == 0) {  // exclusive scan of the kRcParts partial counts, which lie in entry order
       const uint32_t c = s_cnt[lane];
-      uint32_t incl = c;
-#pragma unroll
-      for (int s = 1; s < kWave; s <<= 1) {
-        const uint32_t up = __shfl_up(incl, s, kWave);
-        if (lane >= static_cast<uint32_t>(s)) incl += up;
-      }
-      s_base[lane] = incl - c;
+      s_base[lane] = wave_inclusive_sum(c, lane) - c;
     }
     __syncthreads();
 #pragma unroll
@@ -333,7 +256,7 @@ static void rc_describe(const hdk_hip_plan* p, uint32_t entry_count, const int64
 using namespace hdk;
 
 extern "C" size_t hdk_hip_result_columns_workspace_bytes(uint32_t entry_count) {
-  return ((rc_tiles(entry_count) + 1) * sizeof(uint32_t) + 255) & ~static_cast<size_t>(255);
+  return align256((rc_tiles(entry_count) + 1) * sizeof(uint32_t));
 }
 
 extern "C" int32_t hdk_hip_columnarize_result(const hdk_hip_plan* plan, const int64_t* buf, uint32_t entry_count,
@@ -357,18 +280,13 @@ extern "C" int32_t hdk_hip_columnarize_result(const hdk_hip_plan* plan, const in
   RcDesc d;
   rc_describe(plan, entry_count, init_vals, &d);
   AsyncScratch mem(s);
-  if (!workspace) {
-    HDK_HIP_CHECK(hipMallocAsync(&mem.p, need, s));
-    workspace = mem.p;
-  }
+  st = acquire_workspace(mem, &workspace, need);
+  if (st) return st;
   uint32_t* tiles = static_cast<uint32_t*>(workspace);
   const uint32_t ntiles = static_cast<uint32_t>(rc_tiles(entry_count));
   const int8_t* table = reinterpret_cast<const int8_t*>(buf);
   const bool row16 = !plan->output_columnar && plan->row_size_quad == 2 && reinterpret_cast<uintptr_t>(buf) % 16 == 0;
-  const hdk_hip_device_properties* props = device_props(device_id);
-  size_t blocks = static_cast<size_t>(props->num_cu) * 8;
-  if (blocks > ntiles) blocks = ntiles;
-  const dim3 grid(static_cast<unsigned>(blocks)), block(kRcBlock);
+  const dim3 grid(persistent_grid(device_props(device_id), ntiles)), block(kRcBlock);
   if (ntiles) {
     if (row16) {
       hipLaunchKernelGGL(hdk_result_count<true>, grid, block, 0, s, table, entry_count, d.probe, ntiles, tiles);
@@ -376,7 +294,7 @@ extern "C" int32_t hdk_hip_columnarize_result(const hdk_hip_plan* plan, const in
       hipLaunchKernelGGL(hdk_result_count<false>, grid, block, 0, s, table, entry_count, d.probe, ntiles, tiles);
     }
   }
-  hipLaunchKernelGGL(hdk_result_scan, dim3(1), dim3(kRcScanBlock), 0, s, tiles, ntiles, row_count);
+  launch_counts_scan(tiles, ntiles, kRcScanPer, row_count, s);
   if (ntiles && out_cols && capacity) {
     if (row16) {
       hipLaunchKernelGGL(hdk_result_compact<true>, grid, block, 0, s, table, entry_count, d, ntiles, tiles, out_cols, capacity);

@@ -1414,11 +1414,10 @@ static int32_t launch_join_direct(const hdk_hip_plan* plan, JoinDirectArgs ja, c
   SliceArgs sa;
   if (match_join_sliced(plan, ja, ko, shape.grid, &sa)) {
     // key-range slices probed out of LDS; the row-order kernel below stays armed for what the slices cannot carry
-    auto up = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
     const size_t tw = sa.narrow ? 1 : 2;
     const size_t nsub = static_cast<size_t>(sa.nbins) * kSliceXcds;
-    const size_t b_tuples = up((nsub * sa.sub + sa.cap_ovf) * tw * 8);
-    const size_t b_fill = up((nsub * kSliceCursorStride + 8) * sizeof(uint32_t));
+    const size_t b_tuples = align256((nsub * sa.sub + sa.cap_ovf) * tw * 8);
+    const size_t b_fill = align256((nsub * kSliceCursorStride + 8) * sizeof(uint32_t));
     if (hipMallocAsync(&scratch.p, b_tuples + b_fill, s) == hipSuccess) {
       int8_t* q = static_cast<int8_t*>(scratch.p);
       sa.kp = ja.kp;
@@ -1458,9 +1457,8 @@ static int32_t launch_join_direct(const hdk_hip_plan* plan, JoinDirectArgs ja, c
     ca.sub = ((rows / (kClusterBins * kClusterXcds)) * 17 / 16 + 4096 + 15) & ~15ull;
     ca.cap_ovf = rows;
     const uint64_t nsub = static_cast<uint64_t>(kClusterBins) * kClusterXcds;
-    auto up = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-    const size_t b_tuples = up((nsub * ca.sub + ca.cap_ovf) * ca.ncols * 8);
-    const size_t b_fill = up((nsub * kClusterCursorStride + 4) * sizeof(uint32_t));
+    const size_t b_tuples = align256((nsub * ca.sub + ca.cap_ovf) * ca.ncols * 8);
+    const size_t b_fill = align256((nsub * kClusterCursorStride + 4) * sizeof(uint32_t));
     if (hipMallocAsync(&scratch.p, b_tuples + b_fill, s) == hipSuccess) {
       int8_t* q = static_cast<int8_t*>(scratch.p);
       ca.out[0] = reinterpret_cast<int64_t*>(q);
@@ -1854,13 +1852,12 @@ static int32_t launch_join_sliced2(const hdk_hip_plan* plan, const hdk_hip_plan*
     (void)hipGetLastError();
     return HDK_HIP_OK;
   }
-  auto up = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
   const size_t nsub = static_cast<size_t>(sa.nbins) * kSliceXcds;
-  const size_t b_tuples = up((nsub * sa.sub + sa.cap_ovf) * 8);
-  const size_t b_tuples2 = ga.two_level ? up(static_cast<size_t>(ga.nslices) * ga.cap2 * 8) : 0;
+  const size_t b_tuples = align256((nsub * sa.sub + sa.cap_ovf) * 8);
+  const size_t b_tuples2 = ga.two_level ? align256(static_cast<size_t>(ga.nslices) * ga.cap2 * 8) : 0;
   const size_t n_fill1 = nsub * kSliceCursorStride + 8;
   const size_t n_fill2 = ga.two_level ? static_cast<size_t>(ga.nslices) * kSliceCursorStride : 0;
-  const size_t b_fill = up((n_fill1 + n_fill2) * sizeof(uint32_t));
+  const size_t b_fill = align256((n_fill1 + n_fill2) * sizeof(uint32_t));
   AsyncScratch scratch(s);
   if (hipMallocAsync(&scratch.p, b_tuples + b_tuples2 + b_fill, s) != hipSuccess) {
     (void)hipGetLastError();  // no scratch: the interpreter probes in row order
@@ -2478,12 +2475,11 @@ static int32_t launch_cluster_join(ClusterArgs ca, KernParams* kp, const hdk_hip
   const uint64_t col_rows = nsub * ca.sub + ca.cap_ovf;
   const uint64_t nfr = nsub + 1;
   const uint32_t ntab_max = 1 + HDK_HIP_MAX_JOINS;
-  auto up = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-  const size_t b_cols = up(col_rows * 8) * ca.ncols;
-  const size_t b_fill = up((nsub * kClusterCursorStride + 4) * sizeof(uint32_t));
-  const size_t b_colptrs = up(nfr * ca.ncols_total * sizeof(void*));
-  const size_t b_fragptrs = up(nfr * sizeof(void*));
-  const size_t b_rows = up(nfr * ntab_max * sizeof(int64_t));
+  const size_t b_cols = align256(col_rows * 8) * ca.ncols;
+  const size_t b_fill = align256((nsub * kClusterCursorStride + 4) * sizeof(uint32_t));
+  const size_t b_colptrs = align256(nfr * ca.ncols_total * sizeof(void*));
+  const size_t b_fragptrs = align256(nfr * sizeof(void*));
+  const size_t b_rows = align256(nfr * ntab_max * sizeof(int64_t));
   int8_t* q = nullptr;
   if (hipMallocAsync(reinterpret_cast<void**>(&q), b_cols + b_fill + b_colptrs + b_fragptrs + 2 * b_rows + 256, s) != hipSuccess) {
     (void)hipGetLastError();
@@ -2492,7 +2488,7 @@ static int32_t launch_cluster_join(ClusterArgs ca, KernParams* kp, const hdk_hip
   *scratch = q;
   for (int c = 0; c < ca.ncols; ++c) {
     ca.out[c] = reinterpret_cast<int64_t*>(q);
-    q += up(col_rows * 8);
+    q += align256(col_rows * 8);
   }
   ca.fill = reinterpret_cast<uint32_t*>(q);
   ca.fill_ovf = ca.fill + nsub * kClusterCursorStride;

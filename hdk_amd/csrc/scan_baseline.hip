@@ -399,7 +399,6 @@ static void launch_part_tail(const hdk_hip_plan* plan, PartArgs& pa, const hdk_h
 // scratch of the passes behind level 1, carved from `q` (or just sized when q == nullptr): fine slabs, overflow area,
 // spill segments, [spill list when level 1's slabs are not ours to reuse], cursors
 static size_t part_carve_tail(PartArgs& pa, int8_t* q, bool own_spill_list, size_t* cursor_bytes, uint32_t** cursors) {
-  auto up = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
   const size_t tw = static_cast<size_t>(pa.tw);
   const size_t b2 = static_cast<size_t>(pa.fine_count) * pa.cap2 * tw * 8;
   const size_t bo = static_cast<size_t>(pa.cap_ovf) * tw * 8;
@@ -408,12 +407,12 @@ static size_t part_carve_tail(PartArgs& pa, int8_t* q, bool own_spill_list, size
   const size_t nc = 2 * static_cast<size_t>(pa.fine_count) + 4;  // fill2 | nspill | fill_ovf, fill_spill, fallback
   const size_t bc = nc * sizeof(uint32_t);
   if (q) {
-    pa.slab2 = reinterpret_cast<int64_t*>(q); q += up(b2);
-    pa.ovf = reinterpret_cast<int64_t*>(q); q += up(bo);
-    pa.spill_seg = reinterpret_cast<int64_t*>(q); q += up(bs);
+    pa.slab2 = reinterpret_cast<int64_t*>(q); q += align256(b2);
+    pa.ovf = reinterpret_cast<int64_t*>(q); q += align256(bo);
+    pa.spill_seg = reinterpret_cast<int64_t*>(q); q += align256(bs);
     if (own_spill_list) {
       pa.slab1 = reinterpret_cast<int64_t*>(q);  // (pass 3 and 4 know the shared spill list as `slab1`)
-      q += up(bl);
+      q += align256(bl);
     }
     pa.fill2 = reinterpret_cast<uint32_t*>(q);
     pa.nspill = pa.fill2 + pa.fine_count;
@@ -423,7 +422,7 @@ static size_t part_carve_tail(PartArgs& pa, int8_t* q, bool own_spill_list, size
     *cursors = pa.fill2;
   }
   *cursor_bytes = bc;
-  return up(b2) + up(bo) + up(bs) + up(bl) + up(bc);
+  return align256(b2) + align256(bo) + align256(bs) + align256(bl) + align256(bc);
 }
 
 static int32_t launch_scan_partitioned(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
@@ -440,22 +439,21 @@ static int32_t launch_scan_partitioned(const hdk_hip_plan* plan, const hdk_hip_p
   const uint64_t tile = static_cast<uint64_t>(part_tile(pa.narrow != 0));
   const uint64_t tiles = (pa.total_rows + tile - 1) / tile;
   if (tiles < g1) g1 = static_cast<unsigned>(tiles ? tiles : 1);
-  auto up = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
   const size_t b1 = static_cast<size_t>(pa.p1) * pa.cap1 * tw * 8;
   const size_t bc1 = static_cast<size_t>(pa.p1) * kPartXcds * kPartCursorStride * sizeof(uint32_t);
   size_t bc2 = 0;
   uint32_t* cur2 = nullptr;
   const size_t tail = part_carve_tail(pa, nullptr, false, &bc2, &cur2);
   AsyncScratch scratch(s);
-  const hipError_t me = hipMallocAsync(&scratch.p, up(b1) + up(bc1) + tail, s);
+  const hipError_t me = hipMallocAsync(&scratch.p, align256(b1) + align256(bc1) + tail, s);
   if (me != hipSuccess) {
     (void)hipGetLastError();
     scratch.p = nullptr;
     return kPartitionedNoScratch;  // not an error: the caller takes the global-atomics kernel instead
   }
   int8_t* q = static_cast<int8_t*>(scratch.p);
-  pa.slab1 = reinterpret_cast<int64_t*>(q); q += up(b1);
-  pa.fill1 = reinterpret_cast<uint32_t*>(q); q += up(bc1);
+  pa.slab1 = reinterpret_cast<int64_t*>(q); q += align256(b1);
+  pa.fill1 = reinterpret_cast<uint32_t*>(q); q += align256(bc1);
   part_carve_tail(pa, q, false, &bc2, &cur2);
   HDK_HIP_CHECK(hipMemsetAsync(pa.fill1, 0, bc1, s));
   HDK_HIP_CHECK(hipMemsetAsync(cur2, 0, bc2, s));
@@ -466,7 +464,7 @@ static int32_t launch_scan_partitioned(const hdk_hip_plan* plan, const hdk_hip_p
   if (hdk_sw(SW_PART_TRACE)) {
     fprintf(stderr, "part: scratch %p +%zu | slab1 %p (%zu) fill1 %p (%zu) slab2 %p ovf %p spill_seg %p fill2 %p | p1 %u p2_log2 %u fine %u "
             "cap1 %llu sub1 %llu cap2 %llu cap_ovf %llu cap_spill %llu tw %d slots %u rows %llu table %p\n",
-            scratch.p, up(b1) + up(bc1) + tail, (void*)pa.slab1, b1, (void*)pa.fill1, bc1, (void*)pa.slab2, (void*)pa.ovf,
+            scratch.p, align256(b1) + align256(bc1) + tail, (void*)pa.slab1, b1, (void*)pa.fill1, bc1, (void*)pa.slab2, (void*)pa.ovf,
             (void*)pa.spill_seg, (void*)pa.fill2, pa.p1, pa.p2_log2, pa.fine_count, (unsigned long long)pa.cap1,
             (unsigned long long)pa.sub1, (unsigned long long)pa.cap2, (unsigned long long)pa.cap_ovf,
             (unsigned long long)pa.cap_spill, pa.tw, pa.slots, (unsigned long long)pa.total_rows, (void*)nullptr);
@@ -500,9 +498,8 @@ int32_t exchange_shape(const hdk_hip_plan* plan, const hdk_hip_kernel_options* k
     set_error("plan or table geometry outside the radix-partitioned group-by's shape");
     return HDK_HIP_ERR_UNSUPPORTED;
   }
-  auto up = [](size_t x) { return (x + 255) & ~static_cast<size_t>(255); };
-  pa->seg_header_bytes = up((static_cast<size_t>(pa->p1) * kPartXcds + 2) * sizeof(uint32_t));  // counts, flag, shape tag
-  pa->seg_bytes = pa->seg_header_bytes + up(static_cast<size_t>(pa->p1) * pa->cap1 * pa->tw * 8);
+  pa->seg_header_bytes = align256((static_cast<size_t>(pa->p1) * kPartXcds + 2) * sizeof(uint32_t));  // counts, flag, shape tag
+  pa->seg_bytes = pa->seg_header_bytes + align256(static_cast<size_t>(pa->p1) * pa->cap1 * pa->tw * 8);
   if (out) {
     memset(out, 0, sizeof(*out));
     out->num_owners = static_cast<uint32_t>(num_owners);
@@ -514,7 +511,7 @@ int32_t exchange_shape(const hdk_hip_plan* plan, const hdk_hip_kernel_options* k
     out->segment_header_bytes = pa->seg_header_bytes;
     out->segment_bytes = pa->seg_bytes;
     out->rows_bound = ko->total_rows;
-    out->scatter_workspace_bytes = kPlanRegionBytes + up(exchange_cursor_bytes(*pa));
+    out->scatter_workspace_bytes = kPlanRegionBytes + align256(exchange_cursor_bytes(*pa));
     size_t bc2 = 0;
     uint32_t* cur2 = nullptr;
     PartArgs tmp = *pa;
@@ -847,7 +844,6 @@ static bool match_perfect_partitioned(const hdk_hip_plan* p, const hdk_hip_kerne
   a->cap1 = ((rows / nsub) * 5 / 4 + 4096 + 15) & ~15ull;
   a->cap2 = ((rows / a->nslices) * 5 / 4 + 1024 + 15) & ~15ull;
   if (a->cap1 > 0xFFFFFFF0ull || a->cap2 > 0xFFFFFFF0ull) return false;
-  auto up = [](size_t b) { return (b + 255) & ~static_cast<size_t>(255); };
   l->tw = 1 + a->nargs;
   if (a->nargs == 1 && arg_col[0] >= 0 && !any_expr && !(ko->flags & HDK_HIP_LAUNCH_WIDE_TUPLES)) {
     const hdk_hip_col& c = p->cols[arg_col[0]];
@@ -867,11 +863,11 @@ static bool match_perfect_partitioned(const hdk_hip_plan* p, const hdk_hip_kerne
     }
   }
   l->off_fill1 = 256;
-  l->off_fill2 = l->off_fill1 + up(nsub * kPbCursorStride * 4);
-  l->cursor_bytes = l->off_fill2 + (a->two_level ? up(static_cast<size_t>(a->nslices) * kPbCursor2Stride * 4) : 0);
+  l->off_fill2 = l->off_fill1 + align256(nsub * kPbCursorStride * 4);
+  l->cursor_bytes = l->off_fill2 + (a->two_level ? align256(static_cast<size_t>(a->nslices) * kPbCursor2Stride * 4) : 0);
   l->off_t1 = l->cursor_bytes;
-  l->off_t2 = l->off_t1 + up(nsub * a->cap1 * l->tw * 8);
-  l->total = l->off_t2 + (a->two_level ? up(static_cast<size_t>(a->nslices) * a->cap2 * l->tw * 8) : 0);
+  l->off_t2 = l->off_t1 + align256(nsub * a->cap1 * l->tw * 8);
+  l->total = l->off_t2 + (a->two_level ? align256(static_cast<size_t>(a->nslices) * a->cap2 * l->tw * 8) : 0);
   return true;
 }
 

@@ -426,7 +426,7 @@ int32_t launch_bh_packed(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, c
   const uint32_t list_cap = std::min<uint32_t>(cap, 2 * (cap / slices));
   const size_t list_bytes = staged ? static_cast<size_t>(slices) * groups1 * list_cap * 40 : 0;
   const size_t count_bytes = staged ? static_cast<size_t>(slices) * groups1 * 4 : 0;
-  const size_t slabs_total = (slab_bytes * grid + 255) & ~static_cast<size_t>(255);
+  const size_t slabs_total = align256(slab_bytes * grid);
   if (!direct_fold && hipMallocAsync(&scratch.p, slabs_total + list_bytes + count_bytes, s) == hipSuccess) {
     a.slabs = static_cast<uint32_t*>(scratch.p);
     a.num_slabs = grid;

@@ -442,11 +442,11 @@ static bool match_bhm_part(const hdk_hip_plan* p, const hdk_hip_kernel_options* 
   pg->sample_stride = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>(ko->total_rows / (256ull * (16 / g->width)) / 1536, 1), 1u << 16));
   if (const char* e = hdk_sw(SW_BHM_PART_SAMPLE_STRIDE)) pg->sample_stride = static_cast<uint32_t>(std::max(1, atoi(e)));  // (tests)
   l->cursor_bytes = static_cast<size_t>(pg->nbins) * kPbXcds * kPbCursorStride * sizeof(uint32_t) + kBlWords * sizeof(uint32_t);
-  l->cursor_bytes = (l->cursor_bytes + 255) & ~static_cast<size_t>(255);
+  l->cursor_bytes = align256(l->cursor_bytes);
   // (after pass B the tuples are spent and their space takes the ONE slab the eight are reduced to: at least that much)
   // (+ one batch of slack: a clamped claim of the last sub-slab, scan_bhm_part.h)
   l->tuple_bytes = std::max((static_cast<size_t>(kPbXcds) * pg->region_max + kBhmPartBlock * 16) * pg->tw, static_cast<size_t>(total) * a->wpe * 8);
-  l->tuple_bytes = (l->tuple_bytes + 255) & ~static_cast<size_t>(255);
+  l->tuple_bytes = align256(l->tuple_bytes);
   l->slab_bytes = static_cast<size_t>(kPbXcds) * total * a->wpe * 8;
   if (l->slab_bytes > (1ull << 30)) return false;  // (PHM005's 1 M entries: 700 MB of slabs, written and read once)
   l->total = 256 + l->cursor_bytes + l->tuple_bytes + l->slab_bytes;
@@ -690,7 +690,7 @@ static int32_t launch_bhm_part(const hdk_hip_plan* plan, const hdk_hip_plan* d_p
     ia.words = static_cast<uint64_t>(kPbXcds) * pg.total_entries * static_cast<uint32_t>(a.wpe);
     ia.wpe = a.wpe;
     for (int w = 0; w < a.wpe; ++w) ia.wop[w] = g.wop[w];
-    const unsigned gi = static_cast<unsigned>(std::min<uint64_t>((ia.words + 255) / 256, static_cast<uint64_t>(props->num_cu) * 8));
+    const unsigned gi = persistent_grid(props, (ia.words + 255) / 256);
     hipLaunchKernelGGL(hdk_bhm_slab_init<0>, dim3(gi), dim3(256), 0, s, ia);
     HDK_HIP_CHECK(hipGetLastError());
   }
@@ -744,7 +744,7 @@ int32_t launch_bhm(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const K
   // the blocks' slabs, and -- when there are many -- the few slabs they are reduced to before the fold
   const uint32_t words = a.entries * static_cast<uint32_t>(a.wpe);
   const uint32_t red_groups = grid > 16 ? 4u : 0u;
-  const size_t slab_bytes = (static_cast<size_t>(grid) * words * 8 + 255) & ~static_cast<size_t>(255);
+  const size_t slab_bytes = align256(static_cast<size_t>(grid) * words * 8);
   const size_t red_bytes = static_cast<size_t>(red_groups) * words * 8;
   AsyncScratch scratch(s);
   if (hipMallocAsync(&scratch.p, 256 + slab_bytes + red_bytes, s) != hipSuccess) {

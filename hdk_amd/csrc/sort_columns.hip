@@ -12,7 +12,7 @@
 // stream (no block ever waits for another block):
 //   hdk_sort_build_keys   column (read through the current permutation from the second round on) -> keys, row indices
 //                         of the first round, and the census: OR and OR-of-complement of all keys -> which digits are live
-//   per LIVE digit        hdk_sort_hist (per-tile digit counts, digit-major) -> hdk_sort_scan (one block, exclusive scan of
+//   per LIVE digit        hdk_sort_hist (per-tile digit counts, digit-major) -> hdk_counts_scan<16> (one block, exclusive scan of
 //                         256 x tiles counters) -> hdk_sort_scatter (stable ranks recomputed, pairs written to base + rank)
 //   hdk_sort_gather       out_cols[t][r] = cols[t][perm[offset + r]], perm_out[r] = perm[offset + r]
 // The host reads the 16-byte census back once per order entry (one stream synchronisation each) and launches only the
@@ -24,20 +24,19 @@
 // only they are sorted, by all entries.  Ties at the threshold key stay in, so the result is word for word the full sort's.
 #include <string.h>
 
-#include "device_common.h"
+#include "column_primitives.h"
 #include "host_common.h"
 
 namespace hdk {
 
-constexpr int kScBlock = 256;
+constexpr int kScBlock = kTileBlock;
 constexpr int kScItems = 16;  // rows per thread and tile
 constexpr int kScWaves = kScBlock / kWave;
 constexpr uint32_t kScWaveSpan = kScItems * kWave;     // a wave owns 1 024 consecutive rows of its tile, ...
 constexpr uint32_t kScTile = kScWaveSpan * kScWaves;   // ... a tile is 4 096 rows: order inside = (wave, item, lane)
 constexpr int kScDigits = 256;
 static_assert(kScBlock == kScDigits, "one thread per digit value");
-constexpr int kScScanBlock = 1024;
-constexpr int kScScanPer = 16;  // counters per thread and trip
+constexpr ScanPer kScScanPer = SCAN_PER_16;  // counters per thread and trip of the scan
 
 struct ScKeySpec {
   int64_t null_bits;
@@ -76,10 +75,6 @@ HDK_DEV uint64_t sc_key(int64_t w, const ScKeySpec& k) {
     return u < k.null_key ? u + 1 : u;
   }
   return u > k.null_key ? u - 1 : u;
-}
-
-HDK_DEV uint32_t sc_lane_rank(uint64_t mask) {  // set bits of `mask` below this lane
-  return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
 }
 
 // the valid lanes of this wave that hold the same digit (all 64 lanes call this together; the result of an invalid lane
@@ -184,58 +179,12 @@ __global__ __launch_bounds__(kScBlock) void hdk_sort_hist(const uint64_t* __rest
     const bool valid = e0 + static_cast<uint32_t>(j) * kWave < n;
     const uint32_t digit = static_cast<uint32_t>(key[j] >> shift) & 255u;
     const uint64_t mask = sc_match(digit, valid);
-    if (valid && sc_lane_rank(mask) == 0) {  // the lowest lane of each digit adds for all of them
+    if (valid && lane_rank(mask) == 0) {  // the lowest lane of each digit adds for all of them
       atomicAdd(&s_hist[digit], static_cast<uint32_t>(__popcll(mask)));
     }
   }
   __syncthreads();
   counters[static_cast<size_t>(threadIdx.x) * ntiles + blockIdx.x] = s_hist[threadIdx.x];
-}
-
-// counts[0 .. ncount) -> exclusive offsets in place; the total (< 2^32: it counts rows) -> *total when asked for
-__global__ __launch_bounds__(kScScanBlock) void hdk_sort_scan(uint32_t* __restrict__ counts, uint32_t ncount,
-                                                               uint32_t* __restrict__ total_out) {
-  __shared__ uint32_t s_wave[kScScanBlock / kWave];
-  const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  uint32_t carry = 0;
-  for (uint32_t base = 0; base < ncount; base += kScScanBlock * kScScanPer) {
-    const uint32_t i0 = base + threadIdx.x * kScScanPer;
-    uint32_t v[kScScanPer];
-    uint32_t mine = 0;
-#pragma unroll
-    for (int k = 0; k < kScScanPer; ++k) {
-      v[k] = i0 + k < ncount ? counts[i0 + k] : 0;
-      mine += v[k];
-    }
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, kWave);
-      if (lane >= static_cast<uint32_t>(d)) incl += up;
-    }
-    if (lane == kWave - 1) {
-      s_wave[wave] = incl;
-    }
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kScScanBlock / kWave; ++w) {
-      const uint32_t c = s_wave[w];
-      before += static_cast<uint32_t>(w) < wave ? c : 0;
-      total += c;
-    }
-    uint32_t run = carry + before + incl - mine;
-#pragma unroll
-    for (int k = 0; k < kScScanPer; ++k) {
-      if (i0 + k < ncount) counts[i0 + k] = run;
-      run += v[k];
-    }
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0 && total_out) {
-    *total_out = carry;
-  }
 }
 
 // pair i of the tile goes to bases[digit * ntiles + tile] + (pairs of the tile before i with the same digit)
@@ -268,7 +217,7 @@ __global__ __launch_bounds__(kScBlock) void hdk_sort_scatter(const uint64_t* __r
     const uint32_t digit = static_cast<uint32_t>(key[j] >> shift) & 255u;
     const uint64_t mask = sc_match(digit, valid);
     const uint32_t before = s_cnt[wave][digit];
-    const uint32_t r = sc_lane_rank(mask);
+    const uint32_t r = lane_rank(mask);
     rank[j] = before + r;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if (valid && r == 0) {
@@ -329,7 +278,7 @@ __global__ __launch_bounds__(kScBlock) void hdk_sort_select_hist(const uint64_t*
     const bool valid = e0 + static_cast<uint32_t>(j) * kWave < n && (key[j] & pmask) == prefix;
     const uint32_t digit = static_cast<uint32_t>(key[j] >> shift) & 255u;
     const uint64_t mask = sc_match(digit, valid);
-    if (valid && sc_lane_rank(mask) == 0) {
+    if (valid && lane_rank(mask) == 0) {
       atomicAdd(&s_hist[digit], static_cast<uint32_t>(__popcll(mask)));
     }
   }
@@ -370,7 +319,6 @@ __global__ __launch_bounds__(kScBlock) void hdk_sort_select_count(const uint64_t
                                                                    const ScSelect* __restrict__ sel,
                                                                    uint32_t* __restrict__ tile_counts) {
   __shared__ uint32_t s_wave[kScWaves];
-  const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   const uint64_t threshold = sel->prefix;
   const uint64_t e0 = sc_first_row(blockIdx.x);
   uint64_t key[kScItems];
@@ -385,18 +333,7 @@ __global__ __launch_bounds__(kScBlock) void hdk_sort_select_count(const uint64_t
     const bool f = e0 + static_cast<uint32_t>(j) * kWave < n && key[j] <= threshold;
     c += static_cast<uint32_t>(__popcll(__builtin_amdgcn_ballot_w64(f)));
   }
-  if (lane == 0) {
-    s_wave[wave] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t sum = 0;
-#pragma unroll
-    for (int w = 0; w < kScWaves; ++w) {
-      sum += s_wave[w];
-    }
-    tile_counts[blockIdx.x] = sum;
-  }
+  block_store_tile_count<false>(s_wave, c, tile_counts + blockIdx.x);
 }
 
 // idx_out[rank] = row, for the rows whose key is <= the threshold key, in row order
@@ -420,7 +357,7 @@ __global__ __launch_bounds__(kScBlock) void hdk_sort_select_compact(const uint64
   for (int j = 0; j < kScItems; ++j) {
     const bool f = e0 + static_cast<uint32_t>(j) * kWave < n && key[j] <= threshold;
     const uint64_t mask = __builtin_amdgcn_ballot_w64(f);
-    rank[j] = run + sc_lane_rank(mask);
+    rank[j] = run + lane_rank(mask);
     run += static_cast<uint32_t>(__popcll(mask));
     flags |= static_cast<uint32_t>(f) << j;
   }
@@ -461,7 +398,6 @@ __global__ __launch_bounds__(kScBlock) void hdk_sort_gather(const int64_t* __res
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
-static size_t sc_align(size_t x) { return (x + 255) & ~static_cast<size_t>(255); }
 static size_t sc_tiles(uint64_t n) { return static_cast<size_t>((n + kScTile - 1) / kScTile); }
 
 // [census 16 B | select state | select histogram] [keys x2] [rows x2] [256 x tiles counters + 1]
@@ -480,7 +416,7 @@ struct ScSpace {
 static size_t sc_carve(uint64_t n, void* base, ScSpace* sp) {
   int8_t* p = static_cast<int8_t*>(base);
   size_t off = kScHeadBytes;
-  const size_t kb = sc_align(static_cast<size_t>(n) * 8), ib = sc_align(static_cast<size_t>(n) * 4);
+  const size_t kb = align256(static_cast<size_t>(n) * 8), ib = align256(static_cast<size_t>(n) * 4);
   if (sp) {
     sp->census = reinterpret_cast<unsigned long long*>(p);
     sp->sel = reinterpret_cast<ScSelect*>(p + kScSelOff);
@@ -492,7 +428,7 @@ static size_t sc_carve(uint64_t n, void* base, ScSpace* sp) {
     sp->counters = reinterpret_cast<uint32_t*>(p + off + 2 * kb + 2 * ib);
   }
   off += 2 * kb + 2 * ib;
-  off += sc_align((sc_tiles(n) * kScDigits + 1) * sizeof(uint32_t));
+  off += align256((sc_tiles(n) * kScDigits + 1) * sizeof(uint32_t));
   return off;
 }
 
@@ -554,9 +490,14 @@ extern "C" int32_t hdk_hip_sort_columns(const int64_t* cols, uint64_t capacity, 
   HDK_REQUIRE(out_capacity >= out_rows, "hdk_hip_sort_columns: out_capacity %llu below the %llu output rows",
               static_cast<unsigned long long>(out_capacity), static_cast<unsigned long long>(out_rows));
   {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(cols), b = reinterpret_cast<uintptr_t>(out_cols);
-    const uint64_t an = static_cast<uint64_t>(num_cols) * capacity * 8, bn = static_cast<uint64_t>(num_cols) * out_capacity * 8;
-    HDK_REQUIRE(a + an <= b || b + bn <= a, "hdk_hip_sort_columns: out_cols overlaps cols");
+    // (perm_out and workspace are not checked: adding them would change behaviour and is a change of its own; a block
+    // of zero bytes -- out_capacity 0, nothing to write -- overlaps nothing)
+    const MemBlock blk[] = {
+        {"cols", reinterpret_cast<uintptr_t>(cols), static_cast<uint64_t>(num_cols) * capacity * 8},
+        {"out_cols", reinterpret_cast<uintptr_t>(out_cols), static_cast<uint64_t>(num_cols) * out_capacity * 8},
+    };
+    const int32_t bad = require_disjoint("hdk_hip_sort_columns", blk, 2);
+    if (bad) return bad;
   }
   const size_t need = hdk_hip_sort_columns_workspace_bytes(num_rows, num_order);
   HDK_REQUIRE(!workspace || workspace_bytes >= need, "hdk_hip_sort_columns: workspace of %zu bytes, %zu needed", workspace_bytes, need);
@@ -567,10 +508,8 @@ extern "C" int32_t hdk_hip_sort_columns(const int64_t* cols, uint64_t capacity, 
   int32_t st = device_enter(device_id, stream, &s);
   if (st) return st;
   AsyncScratch mem(s);
-  if (!workspace) {
-    HDK_HIP_CHECK(hipMallocAsync(&mem.p, need, s));
-    workspace = mem.p;
-  }
+  st = acquire_workspace(mem, &workspace, need);
+  if (st) return st;
   ScSpace sp;
   sc_carve(num_rows, workspace, &sp);
 
@@ -600,8 +539,7 @@ extern "C" int32_t hdk_hip_sort_columns(const int64_t* cols, uint64_t capacity, 
         hipLaunchKernelGGL(hdk_sort_select_pick, dim3(1), dim3(kScDigits), 0, s, sp.sel, sp.sel_hist, static_cast<uint32_t>(8 * d));
       }
       hipLaunchKernelGGL(hdk_sort_select_count, grid, block, 0, s, sp.keys[1], num_rows, sp.sel, sp.counters);
-      hipLaunchKernelGGL(hdk_sort_scan, dim3(1), dim3(kScScanBlock), 0, s, sp.counters, static_cast<uint32_t>(sc_tiles(num_rows)),
-                         static_cast<uint32_t*>(nullptr));
+      launch_counts_scan(sp.counters, static_cast<uint32_t>(sc_tiles(num_rows)), kScScanPer, nullptr, s);
       ScSelect sel;
       HDK_HIP_CHECK(hipMemcpyAsync(&sel, sp.sel, sizeof(sel), hipMemcpyDeviceToHost, s));
       HDK_HIP_CHECK(hipStreamSynchronize(s));
@@ -636,8 +574,7 @@ extern "C" int32_t hdk_hip_sort_columns(const int64_t* cols, uint64_t capacity, 
       if (!((varying >> (8 * d)) & 255u)) continue;  // all keys agree on this digit: no pass
       const uint32_t shift = static_cast<uint32_t>(8 * d);
       hipLaunchKernelGGL(hdk_sort_hist, grid, block, 0, s, sp.keys[cur], m, shift, mtiles, sp.counters);
-      hipLaunchKernelGGL(hdk_sort_scan, dim3(1), dim3(kScScanBlock), 0, s, sp.counters, mtiles * kScDigits,
-                         static_cast<uint32_t*>(nullptr));
+      launch_counts_scan(sp.counters, mtiles * kScDigits, kScScanPer, nullptr, s);
       hipLaunchKernelGGL(hdk_sort_scatter, grid, block, 0, s, sp.keys[cur], sp.idx[cur], m, shift, mtiles, sp.counters,
                          sp.keys[cur ^ 1], sp.idx[cur ^ 1]);
       cur ^= 1;

@@ -89,6 +89,46 @@ class ExecutionResult:
         return int(result_set.non_empty_mask(self.compiled, self.buffer, self.entry_count).sum())
 
 
+# below this many bytes of worst-case output (num_targets x rows x 8) dense columns are made in ONE call into a block of
+# the worst-case row count; above it the rows are counted first and the block is sized exactly
+ONE_CALL_BYTES = 64 << 20
+
+
+def sized_columns(mgr, device_id, num_targets, worst_rows, call, one_call_bytes, drop_empty=False):
+    """Run a stage that writes dense columns and a row count -> (block, capacity, rows).
+    `call(out_ptr, capacity, row_count_ptr)` enqueues the stage; out_ptr None with capacity 0 only counts.  The count is
+    read back after one stream synchronisation per call.  `drop_empty`: no block when no row came back.  The floor of 8
+    bytes on the worst-case block is fetch_columns' (a table of no entries); filter() never gets there with no rows."""
+    d_rows = mgr.alloc(8, device_id)
+    block = None
+
+    def run(out_ptr, capacity):
+        call(out_ptr, capacity, d_rows.ptr)
+        mgr.synchronizeStream(device_id)
+        return int(mgr.to_host(d_rows.ptr, 8, device_id, np.uint64)[0])
+
+    try:
+        if num_targets * worst_rows * 8 <= one_call_bytes:
+            block = mgr.alloc(max(num_targets * worst_rows * 8, 8), device_id)
+            capacity = worst_rows
+            rows = run(block.ptr, capacity)
+        else:
+            rows = capacity = run(None, 0)
+            if rows:
+                block = mgr.alloc(num_targets * rows * 8, device_id)
+                run(block.ptr, capacity)
+        if drop_empty and rows == 0 and block is not None:
+            block.free()
+            block, capacity = None, 0
+    except Exception:
+        if block is not None:
+            block.free()
+        raise
+    finally:
+        d_rows.free()
+    return block, capacity, rows
+
+
 class DeviceColumns:
     """Dense result columns in device memory: what hdk_hip_columnarize_result made of a group-by buffer (the device form
     of the reference's ColumnarResults for a ResultSet that lives in HBM).  One 8-byte column per target, rows in entry
@@ -179,7 +219,7 @@ class DeviceColumns:
             raise
         return DeviceColumns(cp, self.mgr, self.device_id, block, out_rows, out_rows, self.error_code)
 
-    FILTER_ONE_CALL_BYTES = 64 << 20  # as PreparedStep.COLUMNS_ONE_CALL_BYTES
+    FILTER_ONE_CALL_BYTES = ONE_CALL_BYTES
 
     def filter(self, having) -> "DeviceColumns":
         """HAVING on the device (hdk_hip_filter_columns; the reference's filter step over the previous step's result) ->
@@ -205,35 +245,14 @@ class DeviceColumns:
                                      int(lf.lhs_nullable), int(lf.rhs_is_fp), int(lf.rhs_nullable), 0,
                                      A.to_i64(lf.lhs_null_bits), A.to_i64(lf.rhs_null_bits), A.to_i64(lf.rhs_lit))
         ops = (C.c_uint8 * max(len(having.prog), 1))(*having.prog)
-        d_rows = self.mgr.alloc(8, self.device_id)
-        block = None
 
-        def call(out_ptr, capacity):
+        def call(out_ptr, capacity, row_count_ptr):
             check(lib().hdk_hip_filter_columns(self.block.ptr, self.capacity, nt, n, leaves, len(having.leaves), ops,
-                                               len(having.prog), out_ptr, capacity, d_rows.ptr, None, None, 0,
+                                               len(having.prog), out_ptr, capacity, row_count_ptr, None, None, 0,
                                                self.device_id, None))
-            self.mgr.synchronizeStream(self.device_id)
-            return int(self.mgr.to_host(d_rows.ptr, 8, self.device_id, np.uint64)[0])
 
-        try:
-            if nt * n * 8 <= self.FILTER_ONE_CALL_BYTES:
-                block = self.mgr.alloc(nt * n * 8, self.device_id)
-                capacity = n
-                rows = call(block.ptr, capacity)
-            else:
-                rows = capacity = call(None, 0)
-                if rows:
-                    block = self.mgr.alloc(nt * rows * 8, self.device_id)
-                    call(block.ptr, capacity)
-            if rows == 0 and block is not None:
-                block.free()
-                block, capacity = None, 0
-        except Exception:
-            if block is not None:
-                block.free()
-            raise
-        finally:
-            d_rows.free()
+        block, capacity, rows = sized_columns(self.mgr, self.device_id, nt, n, call, self.FILTER_ONE_CALL_BYTES,
+                                              drop_empty=True)
         return DeviceColumns(cp, self.mgr, self.device_id, block, capacity, rows, self.error_code)
 
     def free(self):
@@ -495,9 +514,7 @@ class PreparedStep:
         # QueryExecutionContext.cpp:221-234, surfaces it only when nothing positive happened)
         return ExecutionResult(self.cp, buf[:self.buffer_bytes // 8], self.cp.entry_count, err, total)
 
-    # below this many bytes of worst-case output (num_targets x entry_count x 8) the columns are made in ONE call into
-    # a block of `entry_count` rows; above it the groups are counted first and the block is sized exactly
-    COLUMNS_ONE_CALL_BYTES = 64 << 20
+    COLUMNS_ONE_CALL_BYTES = ONE_CALL_BYTES
 
     def fetch_columns(self, stream_synced=False) -> DeviceColumns:
         """The step's result as dense device columns (hdk_hip_columnarize_result): the buffer stays in HBM, only what
@@ -515,31 +532,12 @@ class PreparedStep:
         p = self.cp.plan
         n, nt = int(self.cp.entry_count), int(p.num_targets)
         iv = np.ascontiguousarray(self.cp.init_vals, dtype=np.int64)
-        d_rows = self.mgr.alloc(8, self.dev)
-        block = None
 
-        def call(out_ptr, capacity):
+        def call(out_ptr, capacity, row_count_ptr):
             check(self.L.hdk_hip_columnarize_result(C.byref(p), self.out_ptr, n, iv.ctypes.data, out_ptr, capacity,
-                                                    d_rows.ptr, None, 0, self.dev, None))
-            self.mgr.synchronizeStream(self.dev)
-            return int(self.mgr.to_host(d_rows.ptr, 8, self.dev, np.uint64)[0])
+                                                    row_count_ptr, None, 0, self.dev, None))
 
-        try:
-            if nt * n * 8 <= self.COLUMNS_ONE_CALL_BYTES:
-                block = self.mgr.alloc(max(nt * n * 8, 8), self.dev)
-                capacity = n
-                rows = call(block.ptr, capacity)
-            else:
-                rows = capacity = call(None, 0)
-                if rows:
-                    block = self.mgr.alloc(nt * rows * 8, self.dev)
-                    call(block.ptr, capacity)
-        except Exception:
-            if block is not None:
-                block.free()
-            raise
-        finally:
-            d_rows.free()
+        block, capacity, rows = sized_columns(self.mgr, self.dev, nt, n, call, self.COLUMNS_ONE_CALL_BYTES)
         return DeviceColumns(self.cp, self.mgr, self.dev, block, capacity, rows, err)
 
     def run(self, stream=None) -> ExecutionResult:

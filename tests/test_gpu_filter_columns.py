@@ -117,7 +117,7 @@ def test_sizes_and_selectivities(mgr, n):
             assert 0 < len(want) <= TILE and want[0] // TILE == want[-1] // TILE == (n // TILE) // 2
 
 
-SCAN_TRIP = 4096  # tile counts hdk_filter_scan takes per trip (kFcScanBlock * kFcScanPer): 16.7 M rows
+SCAN_TRIP = 4096  # tile counts hdk_counts_scan<4> takes per trip (1 024 threads x kFcScanPer): 16.7 M rows
 
 
 @pytest.mark.parametrize("sel", ["sparse", "one_tile_in_the_second_trip", "last_rows_only"])

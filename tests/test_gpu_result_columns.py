@@ -404,6 +404,39 @@ def test_offsets_beyond_4_gib(oracle, mgr):
     assert (got[:, 3:] == POISON).all()
 
 
+# ---- 6b. more tiles than one trip of the scan -------------------------------------------------------------------------------
+SCAN_TRIP = 4096  # tile counts hdk_counts_scan<4> takes per trip (1 024 threads x 4): 16.8 M entries
+TILE = 4096  # entries per tile (hdk_amd/csrc/result_columns.hip: kRcTile)
+
+
+def test_more_tiles_than_one_scan_trip(mgr):
+    """4 098 tiles: the scan's carry crosses a trip boundary with groups in the tiles on both sides of it -- the last
+    three entries of tile 4095 (the last counter of the first trip) and every third entry of tile 4096 (the first
+    counter of the second).  A columnar perfect-hash table of one key and one slot column, built as a raw buffer."""
+    n = SCAN_TRIP * TILE + TILE + 1
+    st = ArrowStorage()
+    st.import_numpy("t", {"k": np.array([0, n - 1], dtype=np.int64), "v": np.array([A.NULL_BIGINT, 1], dtype=np.int64)})
+    cp = compile_query(st, QueryUnit("t", groupby=[ColRef("k")], output_columnar=True, targets=[Agg("sum", ColRef("v"), "s")]))
+    p = cp.plan
+    assert p.query_kind == A.Q_PERFECT_HASH and p.output_columnar and not p.keyless and p.entry_count == n
+    assert p.key_count == 1 and cp.slot_widths == [8] and p.num_targets == 1
+    kept = np.concatenate([np.arange(SCAN_TRIP * TILE - 3, SCAN_TRIP * TILE), np.arange(SCAN_TRIP * TILE, (SCAN_TRIP + 1) * TILE, 3)])
+    buf = np.empty(2 * n, dtype=np.int64)  # [key column | slot column], n * 8 bytes each
+    buf[:n] = A.EMPTY_KEY_64
+    buf[n:] = int(cp.init_vals[0])
+    buf[kept] = kept
+    buf[n + kept] = kept * 7 - 3
+    cap = 2048
+    d_buf = mgr.to_device(buf, 0)
+    try:
+        rows, got = columnarize(mgr, cp, d_buf.ptr, n, capacity=cap)
+    finally:
+        d_buf.free()
+    assert rows == len(kept) == 3 + 1366
+    assert np.array_equal(got[0, :rows], kept * 7 - 3)
+    assert (got[0, rows:] == POISON).all()
+
+
 # ---- 7. rejections --------------------------------------------------------------------------------------------------------
 def test_rejections(mgr, matrix_table):
     L = lib()
