@@ -14,7 +14,7 @@ namespace hdk {
 constexpr uint32_t kBhmMaxLdsBytes = 144u << 10;        // one 1024-thread block per CU
 constexpr uint32_t kBhmSmallLdsBytes = 40u << 10;       // up to here: 256-thread blocks, four on a CU
 constexpr uint32_t kBhmReplicatedBytes = 32u << 10;     // replicas while the table is tiny
-constexpr int64_t kBhmMaxAbsVal = (1ll << 19) - 1;      // |argument| below this keeps a block's row budget at 2^20 or more
+constexpr int64_t kBhmMaxAbsVal = (1ll << 19) - 1;      // |argument| up to this keeps a block's row budget at 2^19 or more
 // (A/B switches; every table here is dense: HDK_HIP_NO_BH_DENSE turns it off with the one-argument dense forms)
 static bool bhm_off() { return hdk_sw(SW_NO_BHM) != nullptr || hdk_sw(SW_NO_BH_LDS) != nullptr || hdk_sw(SW_NO_BH_DENSE) != nullptr; }
 
@@ -35,7 +35,8 @@ struct BhmGeom {
 };
 
 // the part of the match that does not depend on where the table lives: keys, arguments, LDS words per entry
-static bool match_bhm_shape(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, BhmArgs* a, BhmGeom* g, uint32_t* per_entry_out, int64_t* amax_out) {
+// *addend_out: the largest number one row can add to the sum field of a packed word (bhm_rows_per_word)
+static bool match_bhm_shape(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, BhmArgs* a, BhmGeom* g, uint32_t* per_entry_out, int64_t* addend_out) {
   const bool perfect = p->query_kind == HDK_Q_PERFECT_HASH;
   if (bhm_off() || (!perfect && p->query_kind != HDK_Q_BASELINE_HASH)) return false;
   if (!ko || ko->total_rows == 0 || ko->total_rows >= (1ull << 40)) return false;
@@ -127,7 +128,6 @@ static bool match_bhm_shape(const hdk_hip_plan* p, const hdk_hip_kernel_options*
     word_der[w] = -1;
     word_kind[w] = BMW_ROWS;
   }
-  int64_t amax = 1;
   for (int t = 0; t < p->num_targets; ++t) {
     const hdk_hip_target& tg = p->targets[t];
     if (tg.agg == HDK_AGG_SINGLE_VALUE) return false;
@@ -204,7 +204,6 @@ static bool match_bhm_shape(const hdk_hip_plan* p, const hdk_hip_kernel_options*
       info[d].rmin = rmin;
       info[d].rmax = rmax;
     }
-    amax = std::max<int64_t>(amax, std::max<int64_t>(-rmin, rmax));
     if (tg.agg == HDK_AGG_SUM || tg.agg == HDK_AGG_AVG || tg.agg == HDK_AGG_COUNT) info[d].want_packed = true;
     if (tg.agg == HDK_AGG_MAX) info[d].want_max = true;
     if (tg.agg == HDK_AGG_MIN) info[d].want_min = true;
@@ -325,11 +324,25 @@ static bool match_bhm_shape(const hdk_hip_plan* p, const hdk_hip_kernel_options*
     }
   }
   *per_entry_out = 8u * static_cast<uint32_t>(a->npacked) + static_cast<uint32_t>(a->mm_bytes) + (a->rows_packed < 0 ? 4u : 0u);
-  *amax_out = amax;
+  // what a row adds to a packed word's sum field (bhm_update): for `column` and `column +- literal` the unsigned CODE of the
+  // column, value - raw_min + 1 in 1 .. raw_span + 1 -- as large as the statistics are wide, whatever the values' magnitude; for
+  // `column x literal` the signed value itself
+  int64_t addend = 1;
+  for (int d = 0; d < a->nder; ++d) {
+    const BhmDer& der = a->der[d];
+    if (der.packed < 0) continue;
+    const int64_t one = der.mul == 1 ? static_cast<int64_t>(a->src[der.src].raw_span) + 1 : std::max<int64_t>(-info[d].rmin, info[d].rmax);
+    addend = std::max(addend, one);
+  }
+  *addend_out = addend;
   g->nk = a->nkeys;
   g->ns = a->nsrc;
   return true;
 }
+
+// rows one packed word [rows : 24 | sum : 40] may take before it is decoded: rows < 2^24 (kept at 2^23), and the sum field --
+// read back as a signed 40-bit number, bhm_slab_entry -- inside +-(2^39 - 1) when every row adds the largest addend
+static int64_t bhm_rows_per_word(int64_t addend) { return std::min<int64_t>(((1ll << 39) - 1) / addend, 1ll << 23); }
 
 // byte offsets of a replica's arrays for a table of a->entries entries
 static uint64_t bhm_lds_layout(BhmArgs* a, uint32_t per_entry) {
@@ -342,8 +355,8 @@ static uint64_t bhm_lds_layout(BhmArgs* a, uint32_t per_entry) {
 // ONE pass: the whole dense table in a block's LDS
 static bool match_bhm(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, BhmArgs* a, BhmGeom* g) {
   uint32_t per_entry;
-  int64_t amax;
-  if (!match_bhm_shape(p, ko, a, g, &per_entry, &amax)) return false;
+  int64_t addend;
+  if (!match_bhm_shape(p, ko, a, g, &per_entry, &addend)) return false;
   const uint64_t one = bhm_lds_layout(a, per_entry);
   if (one > kBhmMaxLdsBytes) return false;
   uint32_t rep_bytes = (static_cast<uint32_t>(one) + 15u) & ~15u;
@@ -359,9 +372,9 @@ static bool match_bhm(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, B
   // (256-thread blocks: three on a CU measured best -- msbs1 / msphs1 / phm2 at 256 M rows: 1 -> 1.06 / 1.04 / 0.79 ms, 2 -> 0.66 /
   // 0.63 / 0.60, 3 -> 0.63 / 0.60 / 0.60, 4 -> 0.74 / 0.72 / 0.71, 8 -> 0.94 / 0.93 / 0.89: more waves add LDS contention and slabs)
   g->grid_per_cu = g->block == 1024 ? 1 : 3;
-  // rows a block may put into one entry: rows < 2^23, |sum| < 2^39
-  const int64_t by_sum = ((1ll << 39) - 1) / amax;
-  a->max_rows_per_block = static_cast<uint32_t>(std::min<int64_t>(by_sum, 1ll << 23));
+  // rows a block may put into one entry; a block that walks more raises the flag (rows_seen, hdk_scan_agg_bhm) -- under a
+  // caller's grid too
+  a->max_rows_per_block = static_cast<uint32_t>(bhm_rows_per_word(addend));
   return true;
 }
 
@@ -375,8 +388,8 @@ static bool match_bhm_part(const hdk_hip_plan* p, const hdk_hip_kernel_options* 
   memset(pg, 0, sizeof(*pg));
   BhmArgs* a = &pg->b;
   uint32_t per_entry;
-  int64_t amax;
-  if (!match_bhm_shape(p, ko, a, g, &per_entry, &amax)) return false;
+  int64_t addend;
+  if (!match_bhm_shape(p, ko, a, g, &per_entry, &addend)) return false;
   const bool always = hdk_sw(SW_BH_PARTITIONS_ALWAYS) != nullptr;  // (tests: small inputs and tables)
   if (!always && ko->total_rows < (4ull << 20)) return false;
   const uint32_t total = a->entries;
@@ -422,9 +435,8 @@ static bool match_bhm_part(const hdk_hip_plan* p, const hdk_hip_kernel_options* 
   a->max_rows_per_block = 0xFFFFFFFFu;  // (pass B checks its own bound: a sub-slab's capacity)
   // the sub-slabs are sized on the device from a sample of the keys (hdk_bhm_part_sample / _layout): twice what the sample
   // promises a bin.  The allocation has room for a quarter more rows than the launch's bound says there are.
-  const int64_t by_sum = ((1ll << 39) - 1) / amax;
   // one LDS table of pass B takes a GENERATION of tuples (rows in 24 bits, sums in 40); a sub-slab with more is flushed in between
-  uint64_t generation = static_cast<uint64_t>(std::min<int64_t>(by_sum, 1ll << 23)) & ~4095ull;
+  uint64_t generation = static_cast<uint64_t>(bhm_rows_per_word(addend)) & ~4095ull;
   if (const char* e = hdk_sw(SW_BHM_PART_GENERATION)) generation = static_cast<uint64_t>(std::max(1, atoi(e))) * 4096;  // (tests)
   if (generation < 4096) return false;
   pg->generation = static_cast<uint32_t>(generation);
