@@ -89,6 +89,10 @@ static bool project_one_pass(const hdk_hip_kernel_options* ko, const ProjFastArg
 }
 
 uint32_t project_grid(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props) {
+  // a caller's grid is the caller's (include/hdk_hip.h: 0 => library default): the two passes and the interpreters all
+  // stride by gridDim.x.  choose_shape keeps such a grid without asking here; this keeps the answer the same for any other
+  // caller.  (The one-pass kernel has its resident grid either way: its tickets need co-residency.)
+  if (ko && ko->grid_dim_x) return ko->grid_dim_x;
   const bool scalar = (ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_SCALAR)) || needs_join_loops(p);
   const void* k;
   int block;

@@ -61,6 +61,32 @@ def test_projection_nulls_and_limit(oracle):
     assert cols["b1"] == [None if v is None else v + 1 for v in want]
 
 
+def test_projection_cases_oracle_equals_numpy(oracle):
+    """projection_cases.py: for every layout x query the oracle's sorted (pos, targets...) rows are the numpy ones --
+    the expectations are pinned here before a kernel sees them (test_gpu_projection_groups.py)."""
+    import projection_cases as pc
+    for layout in pc.LAYOUTS:
+        case = pc.Case(layout)
+        for name, join in [(f, False) for f in pc.FILTERS] + [(f, True) for f in pc.JOIN_FILTERS]:
+            want = pc.expected_rows(case, name, join=join)
+            if name == "a<-1":
+                assert len(want) == 0
+            elif name == "none":
+                assert len(want) == case.n
+            else:
+                assert 2 <= len(want) < case.n  # (the LIMIT test needs two rows at least)
+            for columnar in (False, True):
+                cp, buf, err, n = run_projection_oracle(oracle, case.st, pc.query(name, columnar, join=join))
+                assert err == 0 and n == len(want), (layout, name, join, columnar)
+                assert np.array_equal(pc.buffer_rows(cp, buf, n), want), (layout, name, join, columnar)
+        # what the cases are there for: c < 500 passes a share above the dense pass's 1/8 overall, a wave of an odd tile
+        # stays below kProjDenseMin = 64 of its 512 rows
+        keep = pc.keep_mask(case, "c<500")
+        assert keep.mean() > 0.125
+        odd = ((case.pos // pc.TILE_ROWS) & 1) == 1
+        assert keep[odd].mean() * 512 < 32 and keep[~odd].mean() * 512 > 128
+
+
 def test_projection_with_join_and_strings(oracle):
     st = ArrowStorage()
     st.import_arrow(pa.table({"key": pa.array([3, 1, 2], pa.int64()), "name": pa.array(["c", "a", "b"])}), "dim")
