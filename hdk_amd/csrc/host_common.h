@@ -25,6 +25,13 @@ void launch_counts_scan(uint32_t* counts, uint32_t n, ScanPer per, uint64_t* tot
 int32_t launch_init_row_wise_indirect(int64_t* const* groupby_buf, const int64_t* init_vals, uint32_t entry_count,
                                       uint32_t key_count, uint32_t key_width, uint32_t row_size_quad, int keyless,
                                       const hdk_hip_device_properties* props, hipStream_t s);
+// HDK_HIP_LAUNCH_INIT_OUTPUT for the strategies that do not fuse it: the init kernel, on the launch stream
+inline int32_t init_row_wise_output(const hdk_hip_plan* plan, int64_t* const* groupby_buf, const int64_t* init_vals,
+                                    const hdk_hip_device_properties* props, hipStream_t s) {
+  const uint32_t key_count = plan->keyless ? 0u : static_cast<uint32_t>(plan->key_count);
+  return launch_init_row_wise_indirect(groupby_buf, init_vals, plan->entry_count, key_count, static_cast<uint32_t>(plan->key_width),
+                                       plan->row_size_quad, plan->keyless, props, s);
+}
 
 #define HDK_HIP_CHECK(expr)                                                                  \
   do {                                                                                       \

@@ -1,5 +1,6 @@
 // host_match.h -- host-side helpers shared by the scan translation units (scan_agg.hip: API + LDS strategies;
-// scan_baseline.hip: open-addressing strategies; scan_project.hip: filter/project), and what they export to each other.
+// scan_baseline.hip: open-addressing strategies; scan_project.hip: filter/project), and what they export to each other
+// (route.h: how a launch is routed to them).
 #pragma once
 #include <string.h>
 
@@ -7,6 +8,7 @@
 #include "switches.h"
 #include "launch_common.h"
 #include "plain_quals.h"
+#include "route.h"
 
 namespace hdk {
 
@@ -195,17 +197,7 @@ int32_t launch_fast_direct(int kw, int vw, const FastArgs& fa, const LaunchShape
 struct ColsArgs;
 int32_t launch_cols(const ColsArgs& ca, const LaunchShape& shape, hipStream_t s);
 
-// ---- scan_baseline.hip: GroupByBaselineHash plans and perfect-hash tables too big for LDS (STRAT_GLOBAL) ----------
-// persistent grid of the kernel that will run (x 4: random atomics make block run times uneven)
-uint32_t baseline_grid(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props);
-// kernel names of the launch, comma separated
-void baseline_describe(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, char* out, size_t out_len);
-// the whole strategy: radix-partitioned passes when the shape allows, else the global-atomics kernels.  `init_output`
-// = HDK_HIP_LAUNCH_INIT_OUTPUT (fused into the partitioned pass 3, or the init kernel first)
-int32_t launch_baseline(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
-                        const hdk_hip_kernel_options* ko, const LaunchShape& shape, bool init_output,
-                        const hdk_hip_device_properties* props, hipStream_t s);
-
+// ---- scan_baseline.hip (its route and launch: route.h) ------------------------------------------------------------------
 // multi-GPU tuple exchange (include/hdk_hip.h); `cursors` / `scratch`: the caller's workspace behind the plan region
 int32_t exchange_shape(const hdk_hip_plan* plan, const hdk_hip_kernel_options* ko, int32_t num_owners,
                        uint32_t owner_entry_count, struct PartArgs* pa, hdk_hip_exchange_shape* out);
@@ -216,12 +208,5 @@ int32_t launch_aggregate_from_ranks(const hdk_hip_plan* plan, const hdk_hip_plan
                                     const hdk_hip_kernel_options* ko, const hdk_hip_exchange_shape* shape,
                                     const int8_t* recv, int8_t* scratch, const hdk_hip_device_properties* props,
                                     hipStream_t s);
-
-// ---- scan_project.hip: Projection plans (STRAT_PROJECT) ---------------------------------------------------------------
-uint32_t project_grid(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props);
-void project_describe(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, char* out, size_t out_len);
-int32_t launch_project(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
-                       const hdk_hip_kernel_options* ko, const LaunchShape& shape, const hdk_hip_device_properties* props,
-                       hipStream_t s);
 
 }  // namespace hdk

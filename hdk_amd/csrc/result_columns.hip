@@ -205,7 +205,7 @@ int32_t validate_plan_layout(const hdk_hip_plan* p);  // scan_agg.hip: the layou
 static size_t rc_tiles(uint32_t entry_count) { return (static_cast<size_t>(entry_count) + kRcTile - 1) / kRcTile; }
 
 // the plan, decoded for a buffer of `entry_count` entries (which may differ from the plan's)
-static void rc_describe(const hdk_hip_plan* p, uint32_t entry_count, const int64_t* init_vals, RcDesc* d) {
+static void rc_desc_of(const hdk_hip_plan* p, uint32_t entry_count, const int64_t* init_vals, RcDesc* d) {
   memset(d, 0, sizeof(*d));
   d->probe = empty_probe_of(p, entry_count, init_vals);
   d->ncols = static_cast<uint32_t>(p->num_targets);
@@ -278,7 +278,7 @@ extern "C" int32_t hdk_hip_columnarize_result(const hdk_hip_plan* plan, const in
   st = device_enter(device_id, stream, &s);
   if (st) return st;
   RcDesc d;
-  rc_describe(plan, entry_count, init_vals, &d);
+  rc_desc_of(plan, entry_count, init_vals, &d);
   AsyncScratch mem(s);
   st = acquire_workspace(mem, &workspace, need);
   if (st) return st;

@@ -728,11 +728,6 @@ static bool match_keys(const hdk_hip_plan* p, const LaunchShape& shape, KeysArgs
 static bool match_cols(const hdk_hip_plan* p, const LaunchShape& shape, ColsArgs* ca);
 static bool match_keys_values(const hdk_hip_plan* p, KeysArgs* ka);
 static bool match_join_direct(const hdk_hip_plan* p, const LaunchShape& shape, JoinDirectArgs* ja);
-// which of the join kernels takes a plan (one place: the launch, its description and its grid agree)
-enum JoinRoute { JOIN_ROUTE_NONE = 0, JOIN_ROUTE_DIRECT = 1, JOIN_ROUTE_SLICED2 = 2 };
-static JoinRoute route_join(const hdk_hip_plan* plan, const LaunchShape& shape, const hdk_hip_kernel_options* ko, JoinDirectArgs* ja,
-                            Slice2Args* ga);
-static bool join_direct_clusters(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko);
 // the counting form keeps 32-bit counters: half the bytes of the 8-byte words the shape was sized for
 static uint32_t keys_lds_bytes(const KeysArgs& ka, const LaunchShape& shape) {
   return ka.nvals ? shape.lds_bytes : shape.lds_bytes / 2;
@@ -761,8 +756,8 @@ __global__ void k_arm_watch(LaunchWatch* w, uint32_t flags, uint32_t watchdog_ms
   w->deadline = __builtin_amdgcn_s_memrealtime() + static_cast<uint64_t>(watchdog_ms) * 100000ull;
 }
 
-LaunchShape choose_shape(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko,
-                         const hdk_hip_device_properties* props) {
+// strategy, replication and LDS arithmetic of a launch; the grid is the caller's, else the route's kernel sizes it (route_launch)
+static LaunchShape base_shape(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props) {
   LaunchShape s;
   WordLayout wl;
   make_word_layout(p, &wl);
@@ -795,72 +790,6 @@ LaunchShape choose_shape(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko
     s.rep = 1;
     s.lds_bytes = 0;
     s.slab_words = 0;
-  }
-  FastArgs fa;
-  int kw = 0, vw = 0;
-  if (!(ko && ko->grid_dim_x) && match_fast(p, s, &fa, &kw, &vw)) {
-    // Blocks per CU of the streaming kernel, measured at 256 M rows (grid sweep 256..2048 blocks):
-    //   16 B/row, one LDS atomic per row (C2), or no key (C1): 2 per CU is best (C2 @1e9 rows: 512
-    //     blocks 2.60 ms, 1024 blocks 2.71 ms -- fewer slabs to fold, same bytes in flight);
-    //   narrow rows carry more LDS atomics per byte streamed and want more waves to hide them:
-    //     COUNT(*) by a 4-byte key (taxi Q1) 4 per CU (4.4 -> 5.6 TB/s), 2-byte key + AVG (taxi Q2)
-    //     3 per CU.
-    const uint32_t cu = static_cast<uint32_t>(props->num_cu);
-    const bool static_ops = fa.nops == 1 || ((fa.nops == 2 || fa.nops == 3) && fa.op_kind[0] == FOP_ADD_ONE &&
-                                             (fa.op_kind[1] == FOP_ADD_U64 || fa.op_kind[1] == FOP_ADD_F64));
-    if (fa.nxq || fa.vform) {
-      s.grid = 3u * cu;  // X mode (24-32 B/row over three or four streamed columns): c2x at 256 M rows 768 blocks 0.960 ms, 1024 1.054, 1280 1.079, 1536 1.035
-    } else if (fa.nquals) {
-      s.grid = 4u * cu;  // filtered: the filter-column gathers want more waves (C2 + WHERE: 1.09 vs 1.14 ms at 2 per CU)
-    } else if (kw == 0 || kw + vw >= 16) {
-      s.grid = 2u * cu;
-    } else if (vw == 0) {
-      s.grid = 4u * cu;
-    } else if (static_ops) {
-      s.grid = 3u * cu;  // taxi Q2 with the compile-time op list: 768 blocks 0.419 ms, 512 0.507, 1024 0.440
-    } else {
-      s.grid = 8u * cu;  // run-time op list (scalar dispatch per op): more waves hide it
-    }
-    const uint32_t lds_limited = static_cast<uint32_t>((160u * 1024u) / (s.lds_bytes + 1024u)) * cu;
-    if (lds_limited >= cu && s.grid > lds_limited) {
-      s.grid = lds_limited;  // a large unreplicated table: fewer blocks fit per CU, keep them all resident
-    }
-  } else if (ColsArgs cols_args; !(ko && ko->grid_dim_x) && !(ko && (ko->flags & (HDK_HIP_LAUNCH_FORCE_GENERIC | HDK_HIP_LAUNCH_FORCE_SCALAR))) &&
-             match_cols(p, s, &cols_args)) {
-    // one column streamed at a time, kColsU x 16 bytes in flight per lane: two 256-thread blocks per CU carry 64 KB per CU
-    const char* per_cu = hdk_sw(SW_COLS_BLOCKS_PER_CU);  // (A/B measurements)
-    s.grid = (per_cu && atoi(per_cu) > 0 ? static_cast<uint32_t>(atoi(per_cu)) : kColsBlocksPerCu) * static_cast<uint32_t>(props->num_cu);
-  } else if (!(ko && ko->grid_dim_x)) {
-    const bool scalar = (ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_SCALAR)) || needs_join_loops(p);
-    const bool generic = ko && (ko->flags & (HDK_HIP_LAUNCH_FORCE_GENERIC | HDK_HIP_LAUNCH_FORCE_SCALAR));
-    const void* k;
-    int block = kBlock;
-    size_t lds_for_occupancy = s.lds_bytes;
-    KeysArgs ka;
-    if (s.strategy == STRAT_LDS && !generic && match_keys(p, s, &ka)) {
-      lds_for_occupancy = keys_lds_bytes(ka, s);
-      block = kKeysBlock;
-      // value form with a table that leaves room for fewer than four blocks per CU: twice the threads per table
-      if (ka.nvals && (160u * 1024u) / (lds_for_occupancy + 1024u) < 4 && !hdk_sw(SW_KEYS_NO_WIDE_BLOCK)) {
-        block = kKeysWideBlock;
-      }
-      s.block = static_cast<uint32_t>(block);
-      k = keys_kernel(ka, s.block);
-    } else if (s.strategy == STRAT_LDS) {
-      k = scalar ? reinterpret_cast<const void*>(hdk_scan_agg_generic)
-                 : (p->num_joins ? (plan_is_single_matching_set_join(p) ? reinterpret_cast<const void*>(hdk_scan_agg_vec_many)
-                                    : plan_has_keyed_join(p)            ? reinterpret_cast<const void*>(hdk_scan_agg_vec_keyed)
-                                                                        : reinterpret_cast<const void*>(hdk_scan_agg_vec_join))
-                                 : reinterpret_cast<const void*>(hdk_scan_agg_vec));
-      block = scalar ? kBlock : kVecBlock;
-    } else if (s.strategy == STRAT_PROJECT) {
-      s.grid = project_grid(p, ko, props);
-      return s;
-    } else {
-      s.grid = baseline_grid(p, ko, props);
-      return s;
-    }
-    s.grid = resident_grid(k, block, lds_for_occupancy, props);
   }
   return s;
 }
@@ -1145,40 +1074,6 @@ static bool match_cols(const hdk_hip_plan* p, const LaunchShape& shape, ColsArgs
   return ca->ncols > 0;
 }
 
-// (same decisions as launch_scan_lds)
-static const char* scan_kernel_name(const hdk_hip_plan* p, const LaunchShape& s, const hdk_hip_kernel_options* ko, bool force_generic,
-                                    bool force_scalar) {
-  FastArgs fa;
-  int kw, vw;
-  if (!force_generic && match_fast(p, s, &fa, &kw, &vw)) return "hdk_scan_agg_direct";
-  ColsArgs ca;
-  if (!force_generic && match_cols(p, s, &ca)) return "hdk_scan_agg_cols";
-  JoinDirectArgs ja;
-  Slice2Args ga;
-  const JoinRoute route = force_generic ? JOIN_ROUTE_NONE : route_join(p, s, ko, &ja, &ga);
-  if (route == JOIN_ROUTE_DIRECT) return "hdk_join_agg_direct";
-  if (route == JOIN_ROUTE_SLICED2) return "hdk_scan_agg_vec_join";  // (armed behind the sliced passes)
-  KeysArgs ka;
-  if (!force_generic && match_keys(p, s, &ka)) return ka.nvals ? "hdk_scan_agg_keys_values" : "hdk_scan_agg_keys";
-  if (needs_join_loops(p) || force_scalar) return "hdk_scan_agg_generic";
-  return p->num_joins ? (plan_is_single_matching_set_join(p) ? "hdk_scan_agg_vec_many"
-                         : plan_has_keyed_join(p)            ? "hdk_scan_agg_vec_keyed"
-                                                             : "hdk_scan_agg_vec_join")
-                      : "hdk_scan_agg_vec";
-}
-
-// A GroupByPerfectHash plan of the packed on-chip kernels' shape (scan_bh_packed.h: one plain key column, every aggregate over
-// one integer column inside its statistics) that would otherwise run on the batched interpreter or -- its table beyond LDS --
-// on the perfect-partitioned / global-atomics kernels: the reference's PerfectHashSingleCol benchmark queries (PHS001-005:
-// count, sum, max, min, avg by x10 ... x100k) are this shape; the interpreter ran them at 7 % of the HBM roofline, and 1 000
-// groups fell to global atomics (1.5 s per 256 M rows, profiles/r05_bh_configs.txt).
-static bool perfect_goes_packed(const hdk_hip_plan* p, const LaunchShape& s, const hdk_hip_kernel_options* ko) {
-  if (p->query_kind != HDK_Q_PERFECT_HASH || !bh_packed_kernel_name(p, ko)) return false;
-  if (s.strategy == STRAT_GLOBAL) return true;
-  if (s.strategy != STRAT_LDS) return false;
-  return strcmp(scan_kernel_name(p, s, ko, false, false), "hdk_scan_agg_vec") == 0;
-}
-
 // ---- hdk_join_agg_direct (scan_join_direct.h): the matcher ------------------------------------------------------------
 static bool jd_leaf_from(const hdk_hip_plan* p, const hdk_hip_leaf& l, int kc, int xc, JdLeaf* out) {
   out->nullable = l.nullable;
@@ -1281,8 +1176,8 @@ static bool join_direct_clusters(const hdk_hip_plan* p, const hdk_hip_kernel_opt
   // Only on request.  Measured on C3 (256 M rows, 160 MB table): pre-pass 1.96 ms + probes over the clustered tuples
   // 3.19 ms (a quarter of them still miss L2: several key ranges are in flight at once) against 5.08 ms in row order --
   // no gain yet; with the table L2-resident this kernel needs 2.06 ms (the interpreter 3.09).
-  (void)p;
-  return (ko->flags & HDK_HIP_LAUNCH_CLUSTER_PROBES) != 0;
+  const hdk_hip_join& jn = p->joins[0];
+  return (ko->flags & HDK_HIP_LAUNCH_CLUSTER_PROBES) != 0 && static_cast<uint64_t>(jn.max_key - jn.min_key) < 0xFFFFFFFFull;
 }
 
 // ---- hdk_join_agg_sliced (scan_join_sliced.h): key-range slices of the join table probed out of LDS ----------------
@@ -1407,12 +1302,17 @@ static int32_t launch_sliced_kernels(SliceArgs& sa, const LaunchShape& shape, co
   return HDK_HIP_OK;
 }
 
-static int32_t launch_join_direct(const hdk_hip_plan* plan, JoinDirectArgs ja, const hdk_hip_kernel_options* ko,
-                                  const LaunchShape& shape, const hdk_hip_device_properties* props, hipStream_t s) {
+struct JoinDirectRoute { JoinDirectArgs ja; SliceArgs sa; };  // what the routes of hdk_join_agg_direct carry (sa: ROUTE_JOIN_SLICED only)
+
+// (no scratch for the passes in front of the row-order kernel, or no block that large: it probes in row order, unarmed)
+static int32_t launch_join_direct(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_kernel_options* ko,
+                                  const hdk_hip_device_properties* props, hipStream_t s) {
+  const LaunchShape& shape = r.shape;
+  JoinDirectArgs& ja = r.as<JoinDirectRoute>().ja;
+  SliceArgs& sa = r.as<JoinDirectRoute>().sa;
   AsyncScratch scratch(s);
   const hdk_hip_join& jn = plan->joins[0];
-  SliceArgs sa;
-  if (match_join_sliced(plan, ja, ko, shape.grid, &sa)) {
+  if (r.kind == ROUTE_JOIN_SLICED) {
     // key-range slices probed out of LDS; the row-order kernel below stays armed for what the slices cannot carry
     const size_t tw = sa.narrow ? 1 : 2;
     const size_t nsub = static_cast<size_t>(sa.nbins) * kSliceXcds;
@@ -1442,7 +1342,7 @@ static int32_t launch_join_direct(const hdk_hip_plan* plan, JoinDirectArgs ja, c
       (void)hipGetLastError();  // no scratch: probe in row order
       scratch.p = nullptr;
     }
-  } else if (join_direct_clusters(plan, ko) && static_cast<uint64_t>(jn.max_key - jn.min_key) < 0xFFFFFFFFull) {
+  } else if (r.kind == ROUTE_JOIN_DIRECT_CLUSTERED) {
     ClusterArgs ca;
     memset(&ca, 0, sizeof(ca));
     ca.kp = ja.kp;
@@ -1832,10 +1732,10 @@ static S2Scatter s2_scatter_kernel(const SliceArgs& sa) {
 
 struct BhBehindSliced {
   const hdk_hip_plan* plan;  // the baseline-hash plan (host)
-  const hdk_hip_kernel_options* ko;
+  BhGeom g;                  // the open-addressing interpreter's table, as its route was matched
   BhDenseFold fold;
 };
-static int32_t launch_join_sliced2(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, Slice2Args& ga,
+static int32_t launch_join_sliced2(const hdk_hip_plan* d_plan, const KernParams& kp, Slice2Args& ga,
                                    const LaunchShape& shape, int64_t* slabs, const hdk_hip_device_properties* props, hipStream_t s,
                                    bool* launched, BhBehindSliced* bh = nullptr) {
   *launched = false;
@@ -1906,7 +1806,7 @@ static int32_t launch_join_sliced2(const hdk_hip_plan* plan, const hdk_hip_plan*
   // armed behind the passes: the batched interpreter over the plan's own columns, in row order -- clustered input, stale
   // statistics, an overflow area that filled up
   if (bh) {
-    int32_t st = launch_bh_vec_armed(bh->plan, d_plan, kp, bh->ko, props, s, sa.mode);
+    int32_t st = launch_bh_vec_armed(bh->g, bh->plan, d_plan, kp, props, s, sa.mode);
     if (st) return st;
     bh->fold.slabs = slabs;
     bh->fold.num_slabs = shape.grid;
@@ -1930,17 +1830,20 @@ static int32_t launch_join_sliced2(const hdk_hip_plan* plan, const hdk_hip_plan*
   return HDK_HIP_OK;  // (`scratch` is freed here, stream-ordered after the kernels above)
 }
 
-static JoinRoute route_join(const hdk_hip_plan* plan, const LaunchShape& shape, const hdk_hip_kernel_options* ko, JoinDirectArgs* ja,
-                            Slice2Args* ga) {
-  const bool direct = match_join_direct(plan, shape, ja);
-  if (direct) {
-    SliceArgs sa;
-    if (match_join_sliced(plan, *ja, ko, shape.grid, &sa) && sa.fast && !hdk_sw(SW_SLICED2_ALWAYS)) {
-      return JOIN_ROUTE_DIRECT;  // BASELINE config 3 itself: SUM(x + payload), its compile-time form
-    }
-  }
-  if (match_join_sliced2(plan, shape, ko, ga)) return JOIN_ROUTE_SLICED2;
-  return direct ? JOIN_ROUTE_DIRECT : JOIN_ROUTE_NONE;
+// the batched interpreter (or the row-at-a-time kernel) that takes a plan of the LDS strategy: any such plan has one
+static RouteKind interpreter_route(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const void** k, int* block) {
+  const bool scalar = (ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_SCALAR)) || needs_join_loops(p);
+  const RouteKind kind = scalar                                 ? ROUTE_GENERIC
+                         : plan_is_single_matching_set_join(p) ? ROUTE_VEC_MANY
+                         : !p->num_joins                       ? ROUTE_VEC
+                                                               : (plan_has_keyed_join(p) ? ROUTE_VEC_KEYED : ROUTE_VEC_JOIN);
+  *block = scalar ? kBlock : kVecBlock;
+  *k = scalar                     ? reinterpret_cast<const void*>(hdk_scan_agg_generic)
+       : kind == ROUTE_VEC_MANY  ? reinterpret_cast<const void*>(hdk_scan_agg_vec_many)
+       : kind == ROUTE_VEC_KEYED ? reinterpret_cast<const void*>(hdk_scan_agg_vec_keyed)
+       : kind == ROUTE_VEC_JOIN  ? reinterpret_cast<const void*>(hdk_scan_agg_vec_join)
+                                 : reinterpret_cast<const void*>(hdk_scan_agg_vec);
+  return kind;
 }
 
 // ---- GroupByBaselineHash behind the sliced join (`GROUP BY dim.dval % 64`) -----------------------------------------
@@ -1948,11 +1851,13 @@ static JoinRoute route_join(const hdk_hip_plan* plan, const LaunchShape& shape, 
 // table -- but the kernel can bound the key itself: payload % m lies in (-m, m).  The plan runs as an INTERNAL perfect-hash
 // plan over that range (the same scatter and LDS passes as C3g, a dense private group table beside every slice); the slabs
 // are folded into the open-addressing table through the reference's probe sequence (scan_bh.hip: hdk_bh_fold_dense).
-static bool baseline_sliced_join_plan(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props,
-                                      hdk_hip_plan* inner, LaunchShape* shape, Slice2Args* ga, BhDenseFold* fold) {
+struct BhBehindSlicedRoute { BhBehindSliced bh; Slice2Args ga; LaunchShape inner_shape; };
+
+// `r` holds the open-addressing interpreter's route (the armed fallback): it becomes this one when the plan has the shape
+bool route_baseline_sliced_join(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props,
+                                RouteSet refused, LaunchRoute* r) {
   if (p->query_kind != HDK_Q_BASELINE_HASH || p->num_joins != 1 || p->key_count != 1 || p->key_width != 8 || p->output_columnar) return false;
   if (!ko || (ko->flags & (HDK_HIP_LAUNCH_FORCE_GLOBAL_ATOMICS | HDK_HIP_LAUNCH_FORCE_PARTITIONED)) || launch_forces_generic(ko)) return false;
-  if (!bh_lds_kernel_name(p, ko)) return false;  // (the armed fallback is the open-addressing interpreter)
   const hdk_hip_expr& ke = p->keys[0];
   if (ke.nsteps != 1 || ke.leaf0.kind != HDK_LEAF_COL) return false;
   const hdk_hip_step& sp = ke.steps[0];
@@ -1962,133 +1867,217 @@ static bool baseline_sliced_join_plan(const hdk_hip_plan* p, const hdk_hip_kerne
   const bool nonneg = kc.has_stats && kc.min_val >= 0;
   const int64_t lo = nonneg ? 0 : -(m - 1), hi = m - 1;
   const bool has_null = ke.nullable != 0;
-  *inner = *p;
-  inner->query_kind = HDK_Q_PERFECT_HASH;
-  inner->keyless = 0;
-  inner->idx_target_as_key = -1;
-  inner->key_min[0] = lo;
-  inner->key_bucket[0] = 0;
-  inner->key_card[0] = static_cast<uint32_t>(hi - lo + 1 + (has_null ? 1 : 0));
-  inner->key_has_nulls[0] = has_null ? 1 : 0;
-  inner->key_null_translated[0] = hi + 1;
-  inner->entry_count = static_cast<uint32_t>(hi - lo + 1 + (has_null ? 1 : 0));
-  *shape = choose_shape(inner, ko, props);
-  if (shape->strategy != STRAT_LDS || !match_join_sliced2(inner, *shape, ko, ga)) return false;
+  hdk_hip_plan inner = *p;
+  inner.query_kind = HDK_Q_PERFECT_HASH;
+  inner.keyless = 0;
+  inner.idx_target_as_key = -1;
+  inner.key_min[0] = lo;
+  inner.key_bucket[0] = 0;
+  inner.key_card[0] = static_cast<uint32_t>(hi - lo + 1 + (has_null ? 1 : 0));
+  inner.key_has_nulls[0] = has_null ? 1 : 0;
+  inner.key_null_translated[0] = hi + 1;
+  inner.entry_count = static_cast<uint32_t>(hi - lo + 1 + (has_null ? 1 : 0));
+  LaunchShape shape = base_shape(&inner, ko, props);
+  if (shape.strategy != STRAT_LDS) return false;
+  if (!ko->grid_dim_x) {
+    const void* k;
+    int block;
+    interpreter_route(&inner, ko, &k, &block);
+    shape.grid = resident_grid(k, block, shape.lds_bytes, props);
+  }
+  // (two views of the same bytes: the interpreter's geometry is copied out before the matcher writes over it, and put back
+  // when this route does not take the plan)
+  const BhGeom g = r->as<BhGeom>();
+  BhBehindSlicedRoute& b = r->as<BhBehindSlicedRoute>();
+  const RouteKind kind = match_join_sliced2(&inner, shape, ko, &b.ga) ? (b.ga.two_level ? ROUTE_BH_BEHIND_SLICED2_TWO_LEVELS : ROUTE_BH_BEHIND_SLICED2)
+                                                                       : ROUTE_BH_VEC_JOIN;
+  if (kind == ROUTE_BH_VEC_JOIN || route_refused(refused, kind)) {
+    r->as<BhGeom>() = g;
+    return false;
+  }
+  r->kind = kind;
+  b.inner_shape = shape;
+  b.bh.g = g;
+  BhDenseFold* fold = &b.bh.fold;
   memset(fold, 0, sizeof(*fold));
-  fold->entries = inner->entry_count;
+  fold->entries = inner.entry_count;
   fold->out_entry_count = p->entry_count;
-  fold->wpe = ga->wpe;
-  for (int w = 0; w < ga->wpe; ++w) fold->wop[w] = ga->wop[w];
-  fold->nword_mask = ga->nword_mask;
+  fold->wpe = b.ga.wpe;
+  for (int w = 0; w < b.ga.wpe; ++w) fold->wop[w] = b.ga.wop[w];
+  fold->nword_mask = b.ga.nword_mask;
   fold->key_lo = lo;
   fold->null_entry = has_null ? static_cast<uint32_t>(hi + 1 - lo) : 0xFFFFFFFFu;
   fold->null_key = ke.null_val;
   return true;
 }
 
-const char* baseline_sliced_join_names(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props) {
-  hdk_hip_plan inner;
-  LaunchShape shape;
-  Slice2Args ga;
-  BhDenseFold fold;
-  if (!baseline_sliced_join_plan(p, ko, props, &inner, &shape, &ga, &fold)) return nullptr;
-  return ga.two_level ? "hdk_join_order_probe,hdk_join_scatter_slices,hdk_join_scatter_level2,hdk_join_agg_sliced2,hdk_scan_agg_bh_vec_join,hdk_bh_fold_dense"
-                      : "hdk_join_order_probe,hdk_join_scatter_slices,hdk_join_agg_sliced2,hdk_scan_agg_bh_vec_join,hdk_bh_fold_dense";
-}
-
-int32_t launch_baseline_sliced_join(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
-                                    const hdk_hip_device_properties* props, hipStream_t s, bool* launched) {
+int32_t launch_baseline_sliced_join(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
+                                    const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, hipStream_t s, bool* launched) {
   *launched = false;
-  hdk_hip_plan inner;
-  LaunchShape shape;
-  Slice2Args ga;
-  BhBehindSliced bh;
-  if (!baseline_sliced_join_plan(plan, ko, props, &inner, &shape, &ga, &bh.fold)) return HDK_HIP_OK;
-  bh.plan = plan;
-  bh.ko = ko;
+  BhBehindSlicedRoute& b = r.as<BhBehindSlicedRoute>();
+  b.bh.plan = plan;
+  const LaunchShape& shape = b.inner_shape;
   AsyncScratch slabs(s);
   if (hipMallocAsync(&slabs.p, static_cast<size_t>(shape.grid) * shape.slab_words * 8, s) != hipSuccess) {
     (void)hipGetLastError();
     slabs.p = nullptr;
     return HDK_HIP_OK;
   }
-  return launch_join_sliced2(&inner, d_plan, kp, ga, shape, static_cast<int64_t*>(slabs.p), props, s, launched, &bh);
+  return launch_join_sliced2(d_plan, kp, b.ga, shape, static_cast<int64_t*>(slabs.p), props, s, launched, &b.bh);
 }
 
-static int32_t launch_scan_lds(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
-                               const LaunchShape& shape, int64_t* slabs, hipStream_t s, bool force_generic,
-                               bool force_scalar, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props) {
-  FastArgs fa;
-  int kw, vw;
-  if (!force_generic && match_fast(plan, shape, &fa, &kw, &vw)) {
-    fa.kp = kp;
-    fa.slabs = slabs;
-    return launch_fast_direct(kw, vw, fa, shape, s);  // (scan_fast.hip: the instantiations live in their own translation unit)
-  }
-  ColsArgs ca;
-  if (!force_generic && match_cols(plan, shape, &ca)) {
-    ca.kp = kp;
-    ca.slabs = slabs;
-    return launch_cols(ca, shape, s);  // (scan_cols.hip)
-  }
-  JoinDirectArgs ja;
-  Slice2Args ga;
-  const JoinRoute route = force_generic ? JOIN_ROUTE_NONE : route_join(plan, shape, ko, &ja, &ga);
-  if (route == JOIN_ROUTE_SLICED2) {
-    bool launched = false;
-    const int32_t st = launch_join_sliced2(plan, d_plan, kp, ga, shape, slabs, props, s, &launched);
-    if (st || launched) return st;
-    // (no scratch / no block this large: fall through to the kernels that probe in row order)
-    if (match_join_direct(plan, shape, &ja)) {
-      ja.kp = kp;
-      ja.slabs = slabs;
-      return launch_join_direct(plan, ja, ko, shape, props, s);
-    }
-  } else if (route == JOIN_ROUTE_DIRECT) {
-    ja.kp = kp;
-    ja.slabs = slabs;
-    return launch_join_direct(plan, ja, ko, shape, props, s);
-  }
-  KeysArgs ka;
-  if (!force_generic && match_keys(plan, shape, &ka)) {
-    ka.kp = kp;
-    ka.slabs = slabs;
-    void* kargs[] = {&ka};
-    const uint32_t kblock = shape.block == kKeysWideBlock ? kKeysWideBlock : kKeysBlock;
-    HDK_HIP_CHECK(hipLaunchKernel(keys_kernel(ka, kblock), dim3(shape.grid), dim3(kblock), kargs, keys_lds_bytes(ka, shape), s));
-    HDK_HIP_CHECK(hipGetLastError());
-    return HDK_HIP_OK;
-  }
-  if (!force_scalar && !needs_join_loops(plan)) {
-    VecArgs v;
-    v.plan = d_plan;
-    v.kp = kp;
-    v.slabs = slabs;
-    v.entry_count = shape.entry_count;
-    v.rep = shape.rep;
-    v.run_if = nullptr;
-    if (plan_is_single_matching_set_join(plan)) {
-      hipLaunchKernelGGL(hdk_scan_agg_vec_many, dim3(shape.grid), dim3(kVecBlock), shape.lds_bytes, s, v);
-    } else if (plan->num_joins && plan_has_keyed_join(plan)) {
-      hipLaunchKernelGGL(hdk_scan_agg_vec_keyed, dim3(shape.grid), dim3(kVecBlock), shape.lds_bytes, s, v);
-    } else if (plan->num_joins) {
-      hipLaunchKernelGGL(hdk_scan_agg_vec_join, dim3(shape.grid), dim3(kVecBlock), shape.lds_bytes, s, v);
+// ---- the LDS strategy: route and launch -----------------------------------------------------------------------------------------
+struct FastRoute { FastArgs fa; int kw, vw; };
+
+// The streaming kernels, the keys kernel (no plan with a join is its: the join matchers behind it read the grid of the interpreter
+// that stays armed behind them), the join kernels, the interpreters.  The grid is the caller's, or sized for the kernel that runs.
+static void route_scan_lds(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, RouteSet refused,
+                           LaunchRoute* r) {
+  LaunchShape& s = r->shape;
+  const bool own_grid = !(ko && ko->grid_dim_x);
+  const bool generic = launch_forces_generic(ko);
+  const uint32_t cu = static_cast<uint32_t>(props->num_cu);
+  FastRoute& f = r->as<FastRoute>();
+  if (!generic && match_fast(p, s, &f.fa, &f.kw, &f.vw)) {
+    r->kind = ROUTE_STREAM_DIRECT;
+    if (!own_grid) return;
+    // Blocks per CU of the streaming kernel, measured at 256 M rows (grid sweep 256..2048 blocks):
+    //   16 B/row, one LDS atomic per row (C2), or no key (C1): 2 per CU is best (C2 @1e9 rows: 512
+    //     blocks 2.60 ms, 1024 blocks 2.71 ms -- fewer slabs to fold, same bytes in flight);
+    //   narrow rows carry more LDS atomics per byte streamed and want more waves to hide them:
+    //     COUNT(*) by a 4-byte key (taxi Q1) 4 per CU (4.4 -> 5.6 TB/s), 2-byte key + AVG (taxi Q2)
+    //     3 per CU.
+    const FastArgs& fa = f.fa;
+    const int kw = f.kw, vw = f.vw;
+    const bool static_ops = fa.nops == 1 || ((fa.nops == 2 || fa.nops == 3) && fa.op_kind[0] == FOP_ADD_ONE &&
+                                             (fa.op_kind[1] == FOP_ADD_U64 || fa.op_kind[1] == FOP_ADD_F64));
+    if (fa.nxq || fa.vform) {
+      s.grid = 3u * cu;  // X mode (24-32 B/row over three or four streamed columns): c2x at 256 M rows 768 blocks 0.960 ms, 1024 1.054, 1280 1.079, 1536 1.035
+    } else if (fa.nquals) {
+      s.grid = 4u * cu;  // filtered: the filter-column gathers want more waves (C2 + WHERE: 1.09 vs 1.14 ms at 2 per CU)
+    } else if (kw == 0 || kw + vw >= 16) {
+      s.grid = 2u * cu;
+    } else if (vw == 0) {
+      s.grid = 4u * cu;
+    } else if (static_ops) {
+      s.grid = 3u * cu;  // taxi Q2 with the compile-time op list: 768 blocks 0.419 ms, 512 0.507, 1024 0.440
     } else {
-      hipLaunchKernelGGL(hdk_scan_agg_vec, dim3(shape.grid), dim3(kVecBlock), shape.lds_bytes, s, v);
+      s.grid = 8u * cu;  // run-time op list (scalar dispatch per op): more waves hide it
     }
-    HDK_HIP_CHECK(hipGetLastError());
-    return HDK_HIP_OK;
+    const uint32_t lds_limited = static_cast<uint32_t>((160u * 1024u) / (s.lds_bytes + 1024u)) * cu;
+    if (lds_limited >= cu && s.grid > lds_limited) {
+      s.grid = lds_limited;  // a large unreplicated table: fewer blocks fit per CU, keep them all resident
+    }
+    return;
   }
-  ScanArgs a;
-  a.plan = d_plan;
-  a.kp = kp;
-  a.slabs = slabs;
-  a.entry_count = shape.entry_count;
-  a.rep = shape.rep;
-  a.rows_per_tile = kBlock * 4;
-  hipLaunchKernelGGL(hdk_scan_agg_generic, dim3(shape.grid), dim3(kBlock), shape.lds_bytes, s, a);
-  HDK_HIP_CHECK(hipGetLastError());
-  return HDK_HIP_OK;
+  if (!generic && match_cols(p, s, &r->as<ColsArgs>())) {
+    r->kind = ROUTE_COLS;
+    if (!own_grid) return;
+    // one column streamed at a time, kColsU x 16 bytes in flight per lane: two 256-thread blocks per CU carry 64 KB per CU
+    const char* per_cu = hdk_sw(SW_COLS_BLOCKS_PER_CU);  // (A/B measurements)
+    s.grid = (per_cu && atoi(per_cu) > 0 ? static_cast<uint32_t>(atoi(per_cu)) : kColsBlocksPerCu) * cu;
+    return;
+  }
+  KeysArgs& ka = r->as<KeysArgs>();
+  if (!generic && match_keys(p, s, &ka)) {
+    r->kind = ka.nvals ? ROUTE_KEYS_VALUES : ROUTE_KEYS;
+    if (!own_grid) return;
+    const size_t lds = keys_lds_bytes(ka, s);
+    s.block = kKeysBlock;
+    // value form with a table that leaves room for fewer than four blocks per CU: twice the threads per table
+    if (ka.nvals && (160u * 1024u) / (lds + 1024u) < 4 && !hdk_sw(SW_KEYS_NO_WIDE_BLOCK)) s.block = kKeysWideBlock;
+    s.grid = resident_grid(keys_kernel(ka, s.block), static_cast<int>(s.block), lds, props);
+    return;
+  }
+  const void* k;
+  int block;
+  const RouteKind interpreter = interpreter_route(p, ko, &k, &block);
+  if (own_grid) s.grid = resident_grid(k, block, s.lds_bytes, props);
+  if (!generic) {
+    JoinDirectArgs ja;
+    SliceArgs sa;
+    const bool direct = match_join_direct(p, s, &ja);
+    const bool sliced = direct && match_join_sliced(p, ja, ko, s.grid, &sa);
+    // (BASELINE config 3 itself, SUM(x + payload), keeps the compile-time form of its slices)
+    const bool c3_itself = sliced && sa.fast && !hdk_sw(SW_SLICED2_ALWAYS);
+    Slice2Args& ga = r->as<Slice2Args>();
+    if (!c3_itself && match_join_sliced2(p, s, ko, &ga)) {
+      r->kind = ga.two_level ? ROUTE_SLICED2_TWO_LEVELS : ROUTE_SLICED2;
+      if (!route_refused(refused, r->kind)) return;
+      // (no scratch / no block this large: the kernels that probe in row order)
+    }
+    if (direct) {
+      JoinDirectRoute& jd = r->as<JoinDirectRoute>();
+      jd.ja = ja;
+      if (sliced) jd.sa = sa;
+      r->kind = sliced ? ROUTE_JOIN_SLICED : (join_direct_clusters(p, ko) ? ROUTE_JOIN_DIRECT_CLUSTERED : ROUTE_JOIN_DIRECT);
+      return;
+    }
+  }
+  r->kind = interpreter;
+  r->as<const void*>() = k;
+}
+
+// enqueues the scan of an LDS-strategy route; the caller folds the slabs (hdk_finalize)
+static int32_t launch_scan_lds(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, int64_t* slabs,
+                               const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, hipStream_t s, bool* launched) {
+  *launched = true;
+  const LaunchShape& shape = r.shape;
+  switch (r.kind) {
+    case ROUTE_STREAM_DIRECT:
+      r.as<FastRoute>().fa.kp = kp;
+      r.as<FastRoute>().fa.slabs = slabs;  // (scan_fast.hip: the instantiations live in their own translation unit)
+      return launch_fast_direct(r.as<FastRoute>().kw, r.as<FastRoute>().vw, r.as<FastRoute>().fa, shape, s);
+    case ROUTE_COLS:
+      r.as<ColsArgs>().kp = kp;
+      r.as<ColsArgs>().slabs = slabs;
+      return launch_cols(r.as<ColsArgs>(), shape, s);  // (scan_cols.hip)
+    case ROUTE_SLICED2:
+    case ROUTE_SLICED2_TWO_LEVELS:
+      return launch_join_sliced2(d_plan, kp, r.as<Slice2Args>(), shape, slabs, props, s, launched);
+    case ROUTE_JOIN_SLICED:
+    case ROUTE_JOIN_DIRECT:
+    case ROUTE_JOIN_DIRECT_CLUSTERED:
+      r.as<JoinDirectRoute>().ja.kp = kp;
+      r.as<JoinDirectRoute>().ja.slabs = slabs;
+      return launch_join_direct(r, plan, ko, props, s);
+    case ROUTE_KEYS:
+    case ROUTE_KEYS_VALUES: {
+      KeysArgs& ka = r.as<KeysArgs>();
+      ka.kp = kp;
+      ka.slabs = slabs;
+      void* kargs[] = {&ka};
+      const uint32_t kblock = shape.block == kKeysWideBlock ? kKeysWideBlock : kKeysBlock;
+      HDK_HIP_CHECK(hipLaunchKernel(keys_kernel(ka, kblock), dim3(shape.grid), dim3(kblock), kargs, keys_lds_bytes(ka, shape), s));
+      HDK_HIP_CHECK(hipGetLastError());
+      return HDK_HIP_OK;
+    }
+    case ROUTE_GENERIC: {
+      ScanArgs a;
+      a.plan = d_plan;
+      a.kp = kp;
+      a.slabs = slabs;
+      a.entry_count = shape.entry_count;
+      a.rep = shape.rep;
+      a.rows_per_tile = kBlock * 4;
+      hipLaunchKernelGGL(hdk_scan_agg_generic, dim3(shape.grid), dim3(kBlock), shape.lds_bytes, s, a);
+      HDK_HIP_CHECK(hipGetLastError());
+      return HDK_HIP_OK;
+    }
+    default: {  // the batched interpreters: the kernel interpreter_route chose
+      VecArgs v;
+      v.plan = d_plan;
+      v.kp = kp;
+      v.slabs = slabs;
+      v.entry_count = shape.entry_count;
+      v.rep = shape.rep;
+      v.run_if = nullptr;
+      void* kargs[] = {&v};
+      HDK_HIP_CHECK(hipLaunchKernel(r.as<const void*>(), dim3(shape.grid), dim3(kVecBlock), kargs, shape.lds_bytes, s));
+      HDK_HIP_CHECK(hipGetLastError());
+      return HDK_HIP_OK;
+    }
+  }
 }
 
 // value form of hdk_scan_agg_keys: every aggregate argument is a plain column of the outer table (at most two of
@@ -2272,10 +2261,6 @@ static bool match_keys(const hdk_hip_plan* p, const LaunchShape& shape, KeysArgs
   return true;
 }
 
-
-
-
-
 // Head of every launch: the plan copy and the launch's interrupt / watchdog words go to the front of `workspace`
 // (kPlanRegionBytes), the 12 launch pointers become a KernParams.
 int32_t launch_head(const hdk_hip_plan* plan, int8_t* const params[HDK_KP_COUNT], const hdk_hip_kernel_options* ko,
@@ -2330,96 +2315,6 @@ extern "C" int32_t hdk_hip_validate_plan(const hdk_hip_plan* plan, int32_t layou
   return layout_only ? validate_plan_layout(plan) : validate_plan(plan);
 }
 
-extern "C" int32_t hdk_hip_workspace_size(const hdk_hip_plan* plan, const hdk_hip_kernel_options* ko,
-                                          int32_t device_id, size_t* bytes) {
-  HDK_REQUIRE(bytes, "bytes is NULL");
-  const int32_t st = validate_plan(plan);
-  if (st) return st;
-  const hdk_hip_device_properties* props = device_props(device_id);
-  if (!props) return HDK_HIP_ERR_RUNTIME;
-  *bytes = workspace_bytes_for(choose_shape(plan, ko, props));
-  return HDK_HIP_OK;
-}
-
-static bool match_cluster_join(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, ClusterArgs* ca);
-
-extern "C" int32_t hdk_hip_describe_launch(const hdk_hip_plan* plan, const hdk_hip_kernel_options* ko,
-                                           int32_t device_id, char* out, size_t out_len) {
-  HDK_REQUIRE(out && out_len, "out is NULL");
-  const int32_t st = validate_plan(plan);
-  if (st) return st;
-  // (HDK_HIP_DEVICE_ASSUMED_MI355X: the answer for an MI355X without touching a device -- kernel routing is host arithmetic
-  // over the plan, the options and these few numbers, and the CPU test-suite pins it: tests/test_kernel_routing_cpu.py)
-  static const hdk_hip_device_properties assumed = [] {
-    hdk_hip_device_properties p;
-    memset(&p, 0, sizeof(p));
-    p.global_mem = 288ull << 30;
-    p.num_cu = 256;
-    p.max_threads_per_block = 1024;
-    p.wavefront_size = 64;
-    p.grid_size = 4 * 256;
-    p.shared_mem_per_block = 160 << 10;  // (what hipDeviceProp_t::sharedMemPerBlock reports on the MI355X)
-    p.has_shared_memory_atomics = p.can_load_async = p.has_fp64 = 1;
-    strncpy(p.arch_name, "gfx950 (assumed)", sizeof(p.arch_name) - 1);
-    return p;
-  }();
-  const hdk_hip_device_properties* props = device_id == HDK_HIP_DEVICE_ASSUMED_MI355X ? &assumed : device_props(device_id);
-  if (!props) return HDK_HIP_ERR_RUNTIME;
-  const LaunchShape s = choose_shape(plan, ko, props);
-  {
-    ClusterArgs ca;
-    JoinDirectArgs jd;
-    Slice2Args g2;
-    const bool generic = ko && (ko->flags & (HDK_HIP_LAUNCH_FORCE_GENERIC | HDK_HIP_LAUNCH_FORCE_SCALAR));
-    const JoinRoute route = generic ? JOIN_ROUTE_NONE : route_join(plan, s, ko, &jd, &g2);
-    const bool direct = route == JOIN_ROUTE_DIRECT;
-    SliceArgs sl;
-    if (route == JOIN_ROUTE_SLICED2) {
-      const int n = snprintf(out, out_len, g2.two_level ? "hdk_join_order_probe,hdk_join_scatter_slices,hdk_join_scatter_level2,hdk_join_agg_sliced2,"
-                                                        : "hdk_join_order_probe,hdk_join_scatter_slices,hdk_join_agg_sliced2,");
-      if (n > 0 && static_cast<size_t>(n) < out_len) {
-        out += n;
-        out_len -= static_cast<size_t>(n);
-      }
-    } else if (direct && match_join_sliced(plan, jd, ko, s.grid, &sl)) {
-      const int n = snprintf(out, out_len, "hdk_join_order_probe,hdk_join_scatter_slices,hdk_join_agg_sliced,");
-      if (n > 0 && static_cast<size_t>(n) < out_len) {
-        out += n;
-        out_len -= static_cast<size_t>(n);
-      }
-    } else if (direct && join_direct_clusters(plan, ko)) {
-      const int n = snprintf(out, out_len, "hdk_cluster_by_key,");
-      if (n > 0 && static_cast<size_t>(n) < out_len) {
-        out += n;
-        out_len -= static_cast<size_t>(n);
-      }
-    } else if (route == JOIN_ROUTE_NONE && !baseline_sliced_join_names(plan, ko, props) &&
-               match_cluster_join(plan, ko, &ca)) {  // the pre-pass that clusters the outer rows by join-key range
-      const int n = snprintf(out, out_len, "hdk_cluster_by_key,hdk_cluster_params,");
-      if (n > 0 && static_cast<size_t>(n) < out_len) {
-        out += n;
-        out_len -= static_cast<size_t>(n);
-      }
-    }
-  }
-  if (perfect_goes_packed(plan, s, ko)) {
-    snprintf(out, out_len, "%s", bh_packed_kernel_name(plan, ko));
-  } else if (s.strategy == STRAT_LDS) {
-    snprintf(out, out_len, "%s,hdk_finalize",
-             scan_kernel_name(plan, s, ko, ko && (ko->flags & (HDK_HIP_LAUNCH_FORCE_GENERIC | HDK_HIP_LAUNCH_FORCE_SCALAR)),
-                              ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_SCALAR)));
-  } else if (s.strategy == STRAT_PROJECT) {
-    project_describe(plan, ko, out, out_len);
-  } else {
-    if (const char* sj = baseline_sliced_join_names(plan, ko, props)) {  // a bounded key behind a large join table
-      snprintf(out, out_len, "%s", sj);
-    } else {
-      baseline_describe(plan, ko, out, out_len);
-    }
-  }
-  return HDK_HIP_OK;
-}
-
 // ---- clustering pre-pass for join probes (scan_cluster.h) -----------------------------------------------------------
 static bool match_cluster_join(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, ClusterArgs* ca) {
   if (!ko || ko->total_rows == 0 || (ko->flags & HDK_HIP_LAUNCH_NO_CLUSTER_PROBES)) return false;
@@ -2432,12 +2327,10 @@ static bool match_cluster_join(const hdk_hip_plan* p, const hdk_hip_kernel_optio
   if (!plain_outer_col(p, jn.outer_key, &kc)) return false;
   if (jn.max_key < jn.min_key || static_cast<uint64_t>(jn.max_key - jn.min_key) >= 0xFFFFFFFFull) return false;
   const uint64_t range = static_cast<uint64_t>(jn.max_key - jn.min_key) + 1;
-  const uint64_t entry_bytes = jn.kind == HDK_JOIN_ONE_TO_ONE_FUSED ? 8ull * static_cast<uint64_t>(jn.fused_stride) : 4ull;
   // Only on request.  Measured on C3 (256 M rows, 10 M-key dimension, 160 MB fused table): pre-pass 2.2 ms + probes over
   // the clustered rows 4.2 ms against 5.0 ms for probes in row order -- the batched interpreter that consumes the rows
   // needs 3.1 ms even when the whole table sits in L2, so the locality cannot pay for the pre-pass until a specialised
   // consumer exists.
-  (void)entry_bytes;
   if (!(ko->flags & HDK_HIP_LAUNCH_CLUSTER_PROBES)) return false;
   memset(ca, 0, sizeof(*ca));
   for (int i = 0; i < HDK_HIP_MAX_COLS; ++i) ca->outer_slot[i] = -1;
@@ -2532,14 +2425,88 @@ int32_t hdk::launch_finalize_slabs(const hdk_hip_plan* d_plan, const int64_t* sl
   return HDK_HIP_OK;
 }
 
-// HDK_HIP_LAUNCH_INIT_OUTPUT for the strategies that do not fuse it: the init kernel, on the launch stream
-static int32_t init_row_wise_output(const hdk_hip_plan* plan, int8_t* const params[HDK_KP_COUNT], int32_t device_id,
-                                    hipStream_t s) {
-  const uint32_t key_count = plan->keyless ? 0u : static_cast<uint32_t>(plan->key_count);
-  return launch_init_row_wise_indirect(reinterpret_cast<int64_t* const*>(params[HDK_KP_GROUPBY_BUF]),
-                                       reinterpret_cast<const int64_t*>(params[HDK_KP_INIT_AGG_VALS]), plan->entry_count,
-                                       key_count, static_cast<uint32_t>(plan->key_width), plan->row_size_quad,
-                                       plan->keyless, device_props(device_id), s);
+// ---- the routing step (route.h) --------------------------------------------------------------------------------------------------
+// `refused`: routes whose launcher handed the launch back; hdk_hip_describe_launch and hdk_hip_workspace_size route with none.
+static void route_launch(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, RouteSet refused,
+                         LaunchRoute* r) {
+  r->pre = PRE_NONE;
+  r->shape = base_shape(p, ko, props);
+  if (r->shape.strategy == STRAT_PROJECT) {
+    route_project(p, ko, props, r);
+  } else if (r->shape.strategy == STRAT_GLOBAL) {
+    route_baseline(p, ko, props, refused, r);
+  } else {
+    route_scan_lds(p, ko, props, refused, r);
+    // A GroupByPerfectHash plan of the plain batched interpreter that has the packed on-chip kernels' shape (scan_bh_packed.h): the
+    // reference's PerfectHashSingleCol queries (PHS001-005); the interpreter ran them at 7 % of the HBM roofline, and beyond LDS
+    // (route_baseline asks the same kernels first) 1 000 groups took 1.5 s per 256 M rows on global atomics.  The shape stays
+    // the interpreter's, which takes the launch back; the packed matchers write over the route's arguments.
+    const void* const k = r->as<const void*>();
+    if (r->kind == ROUTE_VEC && p->query_kind == HDK_Q_PERFECT_HASH && !route_bh_packed(p, ko, refused, r)) {
+      r->kind = ROUTE_VEC;
+      r->as<const void*>() = k;
+    }
+  }
+  // join probes over a table far larger than L2: permute the outer columns by key range first (scan_cluster.h)
+  if (!route_clusters_its_own_input(r->kind) && match_cluster_join(p, ko, &r->pre_as<ClusterArgs>())) r->pre = PRE_CLUSTER_BY_KEY;
+}
+
+static int32_t launch_route(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, int64_t* slabs,
+                            const hdk_hip_kernel_options* ko, bool* init_output, const hdk_hip_device_properties* props, hipStream_t s,
+                            bool* launched) {
+  if (r.shape.strategy == STRAT_PROJECT) {
+    *launched = true;
+    return launch_project(r, plan, d_plan, kp, ko, props, s);
+  }
+  if (r.shape.strategy == STRAT_GLOBAL) return launch_baseline(r, plan, d_plan, kp, ko, init_output, props, s, launched);
+  if (*init_output) {
+    const int32_t st = init_row_wise_output(plan, kp.groupby_buf, kp.init_agg_vals, props, s);
+    if (st) return st;
+    *init_output = false;
+  }
+  if (!route_fills_slabs(r.kind)) return launch_bh_packed(r, plan, d_plan, kp, ko, props, s, launched);
+  return launch_scan_lds(r, plan, d_plan, kp, slabs, ko, props, s, launched);
+}
+
+extern "C" int32_t hdk_hip_workspace_size(const hdk_hip_plan* plan, const hdk_hip_kernel_options* ko,
+                                          int32_t device_id, size_t* bytes) {
+  HDK_REQUIRE(bytes, "bytes is NULL");
+  const int32_t st = validate_plan(plan);
+  if (st) return st;
+  const hdk_hip_device_properties* props = device_props(device_id);
+  if (!props) return HDK_HIP_ERR_RUNTIME;
+  LaunchRoute r;
+  route_launch(plan, ko, props, 0, &r);
+  *bytes = workspace_bytes_for(r.shape);
+  return HDK_HIP_OK;
+}
+
+extern "C" int32_t hdk_hip_describe_launch(const hdk_hip_plan* plan, const hdk_hip_kernel_options* ko,
+                                           int32_t device_id, char* out, size_t out_len) {
+  HDK_REQUIRE(out && out_len, "out is NULL");
+  const int32_t st = validate_plan(plan);
+  if (st) return st;
+  // (HDK_HIP_DEVICE_ASSUMED_MI355X: the answer for an MI355X without touching a device -- kernel routing is host arithmetic
+  // over the plan, the options and these few numbers, and the CPU test-suite pins it: tests/test_kernel_routing_cpu.py)
+  static const hdk_hip_device_properties assumed = [] {
+    hdk_hip_device_properties p;
+    memset(&p, 0, sizeof(p));
+    p.global_mem = 288ull << 30;
+    p.num_cu = 256;
+    p.max_threads_per_block = 1024;
+    p.wavefront_size = 64;
+    p.grid_size = 4 * 256;
+    p.shared_mem_per_block = 160 << 10;  // (what hipDeviceProp_t::sharedMemPerBlock reports on the MI355X)
+    p.has_shared_memory_atomics = p.can_load_async = p.has_fp64 = 1;
+    strncpy(p.arch_name, "gfx950 (assumed)", sizeof(p.arch_name) - 1);
+    return p;
+  }();
+  const hdk_hip_device_properties* props = device_id == HDK_HIP_DEVICE_ASSUMED_MI355X ? &assumed : device_props(device_id);
+  if (!props) return HDK_HIP_ERR_RUNTIME;
+  LaunchRoute r;
+  route_launch(plan, ko, props, 0, &r);
+  snprintf(out, out_len, "%s%s", r.pre == PRE_CLUSTER_BY_KEY ? "hdk_cluster_by_key,hdk_cluster_params," : "", route_info(r.kind).kernels);
+  return HDK_HIP_OK;
 }
 
 extern "C" int32_t hdk_hip_launch(const hdk_hip_plan* plan, int8_t* const params[HDK_KP_COUNT],
@@ -2555,16 +2522,20 @@ extern "C" int32_t hdk_hip_launch(const hdk_hip_plan* plan, int8_t* const params
   // aggregate kernels start their private tables from the init values (the reference always passes them,
   // QE/QueryExecutionContext.cpp:788-964); a projection has no slots
   HDK_REQUIRE(plan->query_kind == HDK_Q_PROJECTION || params[HDK_KP_INIT_AGG_VALS], "INIT_AGG_VALS is NULL");
+  HDK_REQUIRE(plan->query_kind != HDK_Q_PROJECTION || (params[HDK_KP_MAX_MATCHED] && params[HDK_KP_TOTAL_MATCHED]),
+              "MAX_MATCHED / TOTAL_MATCHED is NULL");
   hipStream_t s;
   st = device_enter(device_id, stream, &s);
   if (st) return st;
   const hdk_hip_device_properties* props = device_props(device_id);
-  const LaunchShape shape = choose_shape(plan, ko, props);
+  LaunchRoute r;
+  route_launch(plan, ko, props, 0, &r);
+  const LaunchShape& shape = r.shape;
   for (int j = 0; j < plan->num_joins; ++j) {
     if (plan->joins[j].kind == HDK_JOIN_ONE_TO_ONE_FUSED) {
       HDK_REQUIRE(plan->joins[j].fused_stride >= 1, "fused join table needs fused_stride >= 1");
-      if ((shape.strategy == STRAT_GLOBAL && !bh_lds_kernel_name(plan, ko)) || (ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_SCALAR)) ||
-          needs_join_loops(plan)) {
+      // ([row id | payloads]: beyond LDS only the on-chip open-addressing kernels read it, nowhere the row-at-a-time kernels)
+      if (shape.strategy == STRAT_GLOBAL ? !route_is_on_chip_bh(r.kind) : (r.kind == ROUTE_GENERIC || r.kind == ROUTE_PROJECT_SCALAR)) {
         set_error("fused join tables are only read by the batched interpreter kernels");
         return HDK_HIP_ERR_UNSUPPORTED;
       }
@@ -2601,48 +2572,27 @@ extern "C" int32_t hdk_hip_launch(const hdk_hip_plan* plan, int8_t* const params
     st = scan_events_begin(device_id, s, &e0, &e1);
     if (st) return st;
   }
-  // join probes over a table far larger than L2: permute the outer columns by key range first (scan_cluster.h)
   AsyncScratch cluster_scratch(s);  // (freed on every way out of the launch)
-  {
-    ClusterArgs ca;
-    JoinDirectArgs jd;
-    Slice2Args g2;
-    const bool generic = ko && (ko->flags & (HDK_HIP_LAUNCH_FORCE_GENERIC | HDK_HIP_LAUNCH_FORCE_SCALAR));
-    // (the direct and the sliced join kernels cluster their own input, as tuples)
-    const JoinRoute route = generic ? JOIN_ROUTE_NONE : route_join(plan, shape, ko, &jd, &g2);
-    // (a baseline-hash plan behind the sliced join clusters its own input, as tuples: launch_baseline_sliced_join)
-    if (route == JOIN_ROUTE_NONE && !baseline_sliced_join_names(plan, ko, props) && match_cluster_join(plan, ko, &ca)) {
-      st = launch_cluster_join(ca, &kp, props, s, &cluster_scratch.p);
-      if (st) return st;
-    }
+  if (r.pre == PRE_CLUSTER_BY_KEY) {
+    st = launch_cluster_join(r.pre_as<ClusterArgs>(), &kp, props, s, &cluster_scratch.p);
+    if (st) return st;
   }
-  if (perfect_goes_packed(plan, shape, ko)) {
-    if (init_output) {
-      st = init_row_wise_output(plan, params, device_id, s);
-      if (st) return st;
-    }
+  int64_t* slabs = reinterpret_cast<int64_t*>(static_cast<int8_t*>(workspace) + kPlanRegionBytes);
+  for (RouteSet refused = 0;;) {
     bool launched = false;
-    st = launch_bh_packed(plan, d_plan, kp, ko, props, s, &launched);
+    st = launch_route(r, plan, d_plan, kp, slabs, ko, &init_output, props, s, &launched);
     if (st) return st;
-    if (launched) {
-      if (timed) {
-        HDK_HIP_CHECK(hipEventRecord(e1, s));
-      }
-      return HDK_HIP_OK;
-    }
+    if (launched) break;
+    // handed back (no scratch memory, no block that large): the next route in the routing order.  Its slabs fit the workspace
+    // checked above: routes that can follow each other share the interpreter's shape (the sliced passes and the packed kernels
+    // keep it), and beyond LDS there are no slabs.  The pre-pass is the first route's: a later `r.pre` is not launched.
+    refused |= RouteSet(1) << r.kind;
+    route_launch(plan, ko, props, refused, &r);
   }
-  if (shape.strategy == STRAT_LDS) {
-    int64_t* slabs = reinterpret_cast<int64_t*>(static_cast<int8_t*>(workspace) + kPlanRegionBytes);
-    if (init_output) {
-      st = init_row_wise_output(plan, params, device_id, s);
-      if (st) return st;
-    }
-    st = launch_scan_lds(plan, d_plan, kp, shape, slabs, s, ko && (ko->flags & (HDK_HIP_LAUNCH_FORCE_GENERIC | HDK_HIP_LAUNCH_FORCE_SCALAR)),
-                         ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_SCALAR), ko, props);
-    if (st) return st;
-    if (timed) {
-      HDK_HIP_CHECK(hipEventRecord(e1, s));
-    }
+  if (timed) {
+    HDK_HIP_CHECK(hipEventRecord(e1, s));
+  }
+  if (route_fills_slabs(r.kind)) {
     FinalizeArgs fa;
     fa.skip_if = nullptr;
     fa.plan = d_plan;
@@ -2653,17 +2603,6 @@ extern "C" int32_t hdk_hip_launch(const hdk_hip_plan* plan, int8_t* const params
     const unsigned fblocks = (shape.entry_count + (kBlock / kWave) - 1) / (kBlock / kWave);
     hipLaunchKernelGGL(hdk_finalize, dim3(fblocks), dim3(kBlock), 0, s, fa);
     HDK_HIP_CHECK(hipGetLastError());
-    return HDK_HIP_OK;
-  }
-  if (shape.strategy == STRAT_PROJECT) {
-    HDK_REQUIRE(params[HDK_KP_MAX_MATCHED] && params[HDK_KP_TOTAL_MATCHED], "MAX_MATCHED / TOTAL_MATCHED is NULL");
-    st = launch_project(plan, d_plan, kp, ko, shape, props, s);
-  } else {
-    st = launch_baseline(plan, d_plan, kp, ko, shape, init_output, props, s);
-  }
-  if (st) return st;
-  if (timed) {
-    HDK_HIP_CHECK(hipEventRecord(e1, s));
   }
   return HDK_HIP_OK;
 }

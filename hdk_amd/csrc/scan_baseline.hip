@@ -426,8 +426,8 @@ static size_t part_carve_tail(PartArgs& pa, int8_t* q, bool own_spill_list, size
 }
 
 static int32_t launch_scan_partitioned(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
-                                       PartArgs pa, const LaunchShape& shape, const hdk_hip_device_properties* props,
-                                       hipStream_t s) {
+                                       PartArgs pa, BaseFastArgs bf, const LaunchShape& shape,
+                                       const hdk_hip_device_properties* props, hipStream_t s) {
   pa.plan = d_plan;
   pa.kp = kp;
   const bool k32 = plan->key_width == 4;
@@ -472,8 +472,6 @@ static int32_t launch_scan_partitioned(const hdk_hip_plan* plan, const hdk_hip_p
   launch_part_scatter<1>(pa, k32, dim3(g1), lds1, s);
   launch_part_tail(plan, pa, props, s);
   // armed fallback: runs only if the scatter passes found the data too skewed for slabs (or the statistics stale)
-  BaseFastArgs bf;
-  match_baseline_fast(plan, &bf);
   bf.plan = d_plan;
   bf.kp = kp;
   bf.entry_count = shape.entry_count;
@@ -609,83 +607,29 @@ int32_t launch_aggregate_from_ranks(const hdk_hip_plan* plan, const hdk_hip_plan
   return HDK_HIP_OK;
 }
 
-static int32_t launch_scan_global(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan,
-                                  const KernParams& kp, const LaunchShape& shape, hipStream_t s, bool force_generic,
+static int32_t launch_scan_global(const hdk_hip_plan* d_plan, const KernParams& kp, uint32_t entry_count, uint32_t grid, hipStream_t s,
                                   const uint32_t* run_if = nullptr) {
-  BaseFastArgs fa;
-  if (!run_if && !force_generic && match_baseline_fast(plan, &fa)) {
-    fa.plan = d_plan;
-    fa.kp = kp;
-    fa.entry_count = shape.entry_count;
-    launch_baseline_direct(plan, fa, shape.grid, s);
-    HDK_HIP_CHECK(hipGetLastError());
-    return HDK_HIP_OK;
-  }
   GlobalArgs a;
   a.plan = d_plan;
   a.kp = kp;
-  a.entry_count = shape.entry_count;
+  a.entry_count = entry_count;
   a.rows_per_tile = kGlobalBlock * 4;
   a.run_if = run_if;
-  hipLaunchKernelGGL(hdk_scan_agg_global, dim3(shape.grid), dim3(kGlobalBlock), 0, s, a);
+  hipLaunchKernelGGL(hdk_scan_agg_global, dim3(grid), dim3(kGlobalBlock), 0, s, a);
   HDK_HIP_CHECK(hipGetLastError());
   return HDK_HIP_OK;
 }
 
+// random atomics make block run times uneven: 4 waves of blocks rebalance the tail
+// (C5 shape: 1792 blocks 21.5 ms, 3584 18.8 ms, 7168 17.6 ms)
+static uint32_t baseline_grid(const void* k, int block, const hdk_hip_device_properties* props) { return resident_grid(k, block, 0, props) * 4; }
+
 int32_t launch_scan_global_armed(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
-                                 const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, hipStream_t s,
-                                 const uint32_t* run_if) {
-  LaunchShape shape;
-  memset(&shape, 0, sizeof(shape));
-  shape.strategy = STRAT_GLOBAL;
-  shape.entry_count = plan->entry_count;
-  shape.grid = baseline_grid(plan, ko, props);
-  return launch_scan_global(plan, d_plan, kp, shape, s, true, run_if);
+                                 const hdk_hip_device_properties* props, hipStream_t s, const uint32_t* run_if) {
+  // (sized for the kernel it runs; behind the perfect-partitioned passes the same kernel keeps the launch shape's grid)
+  return launch_scan_global(d_plan, kp, plan->entry_count, baseline_grid(reinterpret_cast<const void*>(hdk_scan_agg_global), kGlobalBlock, props), s,
+                            run_if);
 }
-
-uint32_t baseline_grid(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props) {
-  BaseFastArgs bf;
-  const void* k;
-  int block;
-  if (!launch_forces_generic(ko) && match_baseline_fast(p, &bf)) {
-    k = baseline_direct_kernel(p);
-    block = kBaseFastBlock;
-  } else {
-    k = reinterpret_cast<const void*>(hdk_scan_agg_global);
-    block = kGlobalBlock;
-  }
-  // random atomics make block run times uneven: 4 waves of blocks rebalance the tail
-  // (C5 shape: 1792 blocks 21.5 ms, 3584 18.8 ms, 7168 17.6 ms)
-  return resident_grid(k, block, 0, props) * 4;
-}
-
-struct PpLayout;
-static bool match_perfect_partitioned(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, PpArgs* a, PpLayout* l);
-static bool perfect_partitioned_takes(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko);
-
-void baseline_describe(const hdk_hip_plan* plan, const hdk_hip_kernel_options* ko, char* out, size_t out_len) {
-  BaseFastArgs fa;
-  PartArgs part;
-  if (const char* bh = bh_lds_kernel_name(plan, ko)) {  // a small table: open addressing in LDS (scan_bh.hip)
-    snprintf(out, out_len, "%s", bh);
-  } else if (!(ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_GLOBAL_ATOMICS)) && match_partitioned(plan, ko, &part)) {
-    snprintf(out, out_len, "hdk_part_scatter,hdk_part_scatter,hdk_part_aggregate,hdk_part_overflow,hdk_scan_agg_baseline_direct");
-  } else if (perfect_partitioned_takes(plan, ko)) {
-    snprintf(out, out_len, "hdk_pp_scatter,hdk_pp_scatter2,hdk_pp_aggregate,hdk_scan_agg_global");
-  } else {
-    snprintf(out, out_len, "%s", !launch_forces_generic(ko) && match_baseline_fast(plan, &fa) ? "hdk_scan_agg_baseline_direct"
-                                                                                               : "hdk_scan_agg_global");
-  }
-}
-
-// HDK_HIP_LAUNCH_INIT_OUTPUT for the strategies that do not fuse it: the init kernel, on the launch stream
-static int32_t init_row_wise_output(const hdk_hip_plan* plan, const KernParams& kp, const hdk_hip_device_properties* props,
-                                    hipStream_t s) {
-  const uint32_t key_count = plan->keyless ? 0u : static_cast<uint32_t>(plan->key_count);
-  return launch_init_row_wise_indirect(kp.groupby_buf, kp.init_agg_vals, plan->entry_count, key_count,
-                                       static_cast<uint32_t>(plan->key_width), plan->row_size_quad, plan->keyless, props, s);
-}
-
 
 // ---- perfect-hash tables beyond LDS: entry-range partitions (scan_agg_perfect_part.h) ---------------------------------------
 struct PpLayout {
@@ -871,12 +815,6 @@ static bool match_perfect_partitioned(const hdk_hip_plan* p, const hdk_hip_kerne
   return true;
 }
 
-static bool perfect_partitioned_takes(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko) {
-  PpArgs a;
-  PpLayout l;
-  return match_perfect_partitioned(p, ko, &a, &l);
-}
-
 template <int TW>
 static void pp_launch(const PpArgs& a, const hdk_hip_device_properties* props, hipStream_t s) {
   constexpr int VR = TW == 1 ? 8 : (TW == 2 ? 4 : 2);
@@ -906,7 +844,7 @@ static void pp_launch(const PpArgs& a, const hdk_hip_device_properties* props, h
 }
 
 // true: the passes (and the armed global-atomics kernel) are on the stream
-static int32_t launch_perfect_partitioned(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, PpArgs& a,
+static int32_t launch_perfect_partitioned(const hdk_hip_plan* d_plan, const KernParams& kp, PpArgs& a,
                                           const PpLayout& l, const LaunchShape& shape, const hdk_hip_device_properties* props,
                                           hipStream_t s, bool* launched) {
   *launched = false;
@@ -940,47 +878,78 @@ static int32_t launch_perfect_partitioned(const hdk_hip_plan* plan, const hdk_hi
     default: pp_launch<3>(a, props, s); break;
   }
   HDK_HIP_CHECK(hipGetLastError());
-  const int32_t st = launch_scan_global(plan, d_plan, kp, shape, s, true, a.flag);  // armed: only when a slab overflowed
+  const int32_t st = launch_scan_global(d_plan, kp, shape.entry_count, shape.grid, s, a.flag);  // armed: only when a slab overflowed
   if (st) return st;
   *launched = true;
   return HDK_HIP_OK;
 }
 
-int32_t launch_baseline(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
-                        const hdk_hip_kernel_options* ko, const LaunchShape& shape, bool init_output,
-                        const hdk_hip_device_properties* props, hipStream_t s) {
-  PartArgs part;
-  if (!bh_lds_kernel_name(plan, ko) && !(ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_GLOBAL_ATOMICS)) && match_partitioned(plan, ko, &part)) {
-    part.init_output = init_output;
-    int32_t st = launch_scan_partitioned(plan, d_plan, kp, part, shape, props, s);
-    if (st == kPartitionedNoScratch) {
-      if (init_output) {
-        st = init_row_wise_output(plan, kp, props, s);
-        if (st) return st;
-      }
-      st = launch_scan_global(plan, d_plan, kp, shape, s, false);
-    }
+// what the routes of this file carry (bf: the direct kernel armed behind the radix passes)
+struct PartRoute { PartArgs part; BaseFastArgs bf; };
+struct PpRoute { PpArgs a; PpLayout l; };
+
+void route_baseline(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, RouteSet refused,
+                    LaunchRoute* r) {
+  // the global-atomics kernel of the plan: the end of the cascade, armed behind the partitioned passes, and what sizes the grid
+  BaseFastArgs bf;
+  const bool fast_shape = match_baseline_fast(p, &bf);
+  const bool direct = fast_shape && !launch_forces_generic(ko);
+  if (!(ko && ko->grid_dim_x)) {
+    r->shape.grid = direct ? baseline_grid(baseline_direct_kernel(p), kBaseFastBlock, props)
+                           : baseline_grid(reinterpret_cast<const void*>(hdk_scan_agg_global), kGlobalBlock, props);
+  }
+  if (route_bh(p, ko, refused, r)) {  // a small table: open addressing in LDS (scan_bh.hip)
+    // (a bounded key behind a large join table: the sliced passes in front of the interpreter)
+    if (r->kind == ROUTE_BH_VEC_JOIN) route_baseline_sliced_join(p, ko, props, refused, r);
+    return;
+  }
+  PartRoute& pr = r->as<PartRoute>();
+  if (!route_refused(refused, ROUTE_RADIX_PARTITIONED) && !(ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_GLOBAL_ATOMICS)) &&
+      match_partitioned(p, ko, &pr.part)) {
+    pr.bf = bf;
+    r->kind = ROUTE_RADIX_PARTITIONED;
+    return;
+  }
+  PpRoute& pp = r->as<PpRoute>();
+  if (!route_refused(refused, ROUTE_PERFECT_PARTITIONED) && match_perfect_partitioned(p, ko, &pp.a, &pp.l)) {
+    r->kind = ROUTE_PERFECT_PARTITIONED;
+    return;
+  }
+  if (direct) r->as<BaseFastArgs>() = bf;
+  r->kind = direct ? ROUTE_BASELINE_DIRECT : ROUTE_GLOBAL;
+}
+
+int32_t launch_baseline(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
+                        const hdk_hip_kernel_options* ko, bool* init_output, const hdk_hip_device_properties* props, hipStream_t s,
+                        bool* launched) {
+  *launched = false;
+  const LaunchShape& shape = r.shape;
+  if (r.kind == ROUTE_RADIX_PARTITIONED) {
+    PartRoute& pr = r.as<PartRoute>();
+    pr.part.init_output = *init_output;  // (fused into pass 3)
+    const int32_t st = launch_scan_partitioned(plan, d_plan, kp, pr.part, pr.bf, shape, props, s);
+    if (st == kPartitionedNoScratch) return HDK_HIP_OK;
+    *init_output = false;
+    *launched = st == HDK_HIP_OK;
     return st;
   }
-  if (init_output) {
-    const int32_t st = init_row_wise_output(plan, kp, props, s);
+  if (*init_output) {
+    const int32_t st = init_row_wise_output(plan, kp.groupby_buf, kp.init_agg_vals, props, s);
     if (st) return st;
+    *init_output = false;
   }
-  {
-    bool launched = false;
-    int32_t st = launch_baseline_sliced_join(plan, d_plan, kp, ko, props, s, &launched);
-    if (st || launched) return st;
-    st = launch_bh_lds(plan, d_plan, kp, ko, props, s, &launched);
-    if (st || launched) return st;
-  }
-  PpArgs pp;
-  PpLayout pl;
-  if (match_perfect_partitioned(plan, ko, &pp, &pl)) {
-    bool launched = false;
-    const int32_t st = launch_perfect_partitioned(plan, d_plan, kp, pp, pl, shape, props, s, &launched);
-    if (st || launched) return st;
-  }
-  return launch_scan_global(plan, d_plan, kp, shape, s, launch_forces_generic(ko));
+  if (route_family(r.kind) == FAM_BH_BEHIND) return launch_baseline_sliced_join(r, plan, d_plan, kp, ko, props, s, launched);
+  if (route_is_on_chip_bh(r.kind)) return launch_bh(r, plan, d_plan, kp, ko, props, s, launched);
+  if (r.kind == ROUTE_PERFECT_PARTITIONED) return launch_perfect_partitioned(d_plan, kp, r.as<PpRoute>().a, r.as<PpRoute>().l, shape, props, s, launched);
+  *launched = true;
+  if (r.kind == ROUTE_GLOBAL) return launch_scan_global(d_plan, kp, shape.entry_count, shape.grid, s);
+  BaseFastArgs& fa = r.as<BaseFastArgs>();
+  fa.plan = d_plan;
+  fa.kp = kp;
+  fa.entry_count = shape.entry_count;
+  launch_baseline_direct(plan, fa, shape.grid, s);
+  HDK_HIP_CHECK(hipGetLastError());
+  return HDK_HIP_OK;
 }
 
 }  // namespace hdk

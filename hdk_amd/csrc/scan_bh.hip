@@ -292,27 +292,22 @@ static const void* bh_kernel(const hdk_hip_plan* p) {
   return p->num_joins ? reinterpret_cast<const void*>(hdk_scan_agg_bh_vec_join) : reinterpret_cast<const void*>(hdk_scan_agg_bh_vec);
 }
 
-const char* bh_lds_kernel_name(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko) {
-  if (const char* pk = bh_packed_kernel_name(p, ko)) return pk;
-  BhGeom g;
-  BhFastArgs fa;
-  int kw, vw, block;
-  if (match_bh_fast(p, ko, &fa, &kw, &vw, &block)) return "hdk_scan_agg_bh_direct";
-  if (!match_bh_lds(p, ko, &g)) return nullptr;
-  return p->num_joins ? "hdk_scan_agg_bh_vec_join" : "hdk_scan_agg_bh_vec";
+struct BhFastRoute { BhFastArgs fa; int kw, vw, block; };  // what the streaming form's route carries
+
+bool route_bh(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, RouteSet refused, LaunchRoute* r) {
+  if (route_bh_packed(p, ko, refused, r)) return true;
+  BhFastRoute& f = r->as<BhFastRoute>();
+  if (match_bh_fast(p, ko, &f.fa, &f.kw, &f.vw, &f.block)) {
+    r->kind = ROUTE_BH_DIRECT;
+    return !route_refused(refused, r->kind);
+  }
+  if (!match_bh_lds(p, ko, &r->as<BhGeom>())) return false;
+  r->kind = p->num_joins ? ROUTE_BH_VEC_JOIN : ROUTE_BH_VEC;
+  return !route_refused(refused, r->kind);
 }
 
-int32_t launch_bh_vec_armed(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
-                            const hdk_hip_device_properties* props, hipStream_t s, const uint32_t* run_if) {
-  BhGeom g;
-  if (!match_bh_lds(plan, ko, &g)) {
-    set_error("the open-addressing interpreter does not take this plan");
-    return HDK_HIP_ERR_UNSUPPORTED;
-  }
-  const void* k = bh_kernel(plan);
-  if (g.lds_bytes > (48u << 10)) {
-    HDK_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(g.lds_bytes)));
-  }
+// the open-addressing interpreter's arguments (slabs: none until a two-level fold gives them)
+static VecArgs bh_vec_args(const BhGeom& g, const hdk_hip_plan* d_plan, const KernParams& kp, const uint32_t* run_if) {
   VecArgs v;
   memset(&v, 0, sizeof(v));
   v.plan = d_plan;
@@ -321,68 +316,64 @@ int32_t launch_bh_vec_armed(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan
   v.rep = g.rep;
   v.run_if = run_if;
   v.bh_cap_log2 = g.cap_log2;
+  return v;
+}
+
+int32_t launch_bh_vec_armed(const BhGeom& g, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
+                            const hdk_hip_device_properties* props, hipStream_t s, const uint32_t* run_if) {
+  const void* k = bh_kernel(plan);
+  if (g.lds_bytes > (48u << 10)) {
+    HDK_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(g.lds_bytes)));
+  }
+  VecArgs v = bh_vec_args(g, d_plan, kp, run_if);
   void* kargs[] = {&v};
   HDK_HIP_CHECK(hipLaunchKernel(k, dim3(resident_grid(k, kVecBlock, g.lds_bytes, props)), dim3(kVecBlock), kargs, g.lds_bytes, s));
   HDK_HIP_CHECK(hipGetLastError());
   return HDK_HIP_OK;
 }
 
-int32_t launch_bh_lds(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
-                      const hdk_hip_device_properties* props, hipStream_t s, bool* launched) {
+int32_t launch_bh(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
+                  const hdk_hip_device_properties* props, hipStream_t s, bool* launched) {
   *launched = false;
-  {
-    const int32_t st = launch_bh_packed(plan, d_plan, kp, ko, props, s, launched);
-    if (st || *launched) return st;
-  }
-  {
-    BhFastArgs fa;
-    int kw, vw, block;
-    if (match_bh_fast(plan, ko, &fa, &kw, &vw, &block)) {
-      fa.plan = d_plan;
-      fa.kp = kp;
-      const void* k = block == 512 ? bh_fast_kernel<512>(kw, vw) : bh_fast_kernel<256>(kw, vw);
-      if (fa.g.lds_bytes > (48u << 10)) {
-        HDK_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(fa.g.lds_bytes)));
-      }
-      // streaming blocks: two per CU of 256 threads (as the perfect-hash kernel runs C2), more while the table is tiny --
-      // narrow rows carry more LDS atomics per byte; one 512-thread block per CU when the table needs the LDS
-      uint32_t grid = resident_grid(k, block, fa.g.lds_bytes, props);
-      const uint32_t cu = static_cast<uint32_t>(props->num_cu);
-      const int per_cu_env = hdk_sw(SW_BH_BLOCKS_PER_CU) ? atoi(hdk_sw(SW_BH_BLOCKS_PER_CU)) : 0;  // (measurements)
-      const uint32_t want = (per_cu_env > 0 ? static_cast<uint32_t>(per_cu_env) : (block == 512 ? 1u : 4u)) * cu;
-      if (grid > want) grid = want;
-      if (ko && ko->grid_dim_x) grid = ko->grid_dim_x;
-      AsyncScratch scratch(s);
-      BhFoldArgs fold;
-      const bool two_level = bh_two_level_fold(scratch, fa.g, fa.ll, grid, s, &fold);
-      fa.slabs = two_level ? static_cast<int64_t*>(scratch.p) : nullptr;
-      void* kargs[] = {&fa};
-      HDK_HIP_CHECK(hipLaunchKernel(k, dim3(grid), dim3(block), kargs, fa.g.lds_bytes, s));
-      HDK_HIP_CHECK(hipGetLastError());
-      if (two_level) {
-        const int32_t st = launch_bh_fold_words(fold, d_plan, kp, s);
-        if (st) return st;
-      }
-      *launched = true;
-      return HDK_HIP_OK;
+  if (route_family(r.kind) != FAM_BH) return launch_bh_packed(r, plan, d_plan, kp, ko, props, s, launched);
+  if (r.kind == ROUTE_BH_DIRECT) {
+    BhFastArgs& fa = r.as<BhFastRoute>().fa;
+    const int kw = r.as<BhFastRoute>().kw, vw = r.as<BhFastRoute>().vw, block = r.as<BhFastRoute>().block;
+    fa.plan = d_plan;
+    fa.kp = kp;
+    const void* k = block == 512 ? bh_fast_kernel<512>(kw, vw) : bh_fast_kernel<256>(kw, vw);
+    if (fa.g.lds_bytes > (48u << 10)) {
+      HDK_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(fa.g.lds_bytes)));
     }
+    // streaming blocks: two per CU of 256 threads (as the perfect-hash kernel runs C2), more while the table is tiny --
+    // narrow rows carry more LDS atomics per byte; one 512-thread block per CU when the table needs the LDS
+    uint32_t grid = resident_grid(k, block, fa.g.lds_bytes, props);
+    const uint32_t cu = static_cast<uint32_t>(props->num_cu);
+    const int per_cu_env = hdk_sw(SW_BH_BLOCKS_PER_CU) ? atoi(hdk_sw(SW_BH_BLOCKS_PER_CU)) : 0;  // (measurements)
+    const uint32_t want = (per_cu_env > 0 ? static_cast<uint32_t>(per_cu_env) : (block == 512 ? 1u : 4u)) * cu;
+    if (grid > want) grid = want;
+    if (ko && ko->grid_dim_x) grid = ko->grid_dim_x;
+    AsyncScratch scratch(s);
+    BhFoldArgs fold;
+    const bool two_level = bh_two_level_fold(scratch, fa.g, fa.ll, grid, s, &fold);
+    fa.slabs = two_level ? static_cast<int64_t*>(scratch.p) : nullptr;
+    void* kargs[] = {&fa};
+    HDK_HIP_CHECK(hipLaunchKernel(k, dim3(grid), dim3(block), kargs, fa.g.lds_bytes, s));
+    HDK_HIP_CHECK(hipGetLastError());
+    if (two_level) {
+      const int32_t st = launch_bh_fold_words(fold, d_plan, kp, s);
+      if (st) return st;
+    }
+    *launched = true;
+    return HDK_HIP_OK;
   }
-  BhGeom g;
-  if (!match_bh_lds(plan, ko, &g)) return HDK_HIP_OK;
+  const BhGeom& g = r.as<BhGeom>();
   const void* k = bh_kernel(plan);
   if (g.lds_bytes > (48u << 10)) {
     HDK_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(g.lds_bytes)));
   }
   const uint32_t grid = (ko && ko->grid_dim_x) ? ko->grid_dim_x : resident_grid(k, kVecBlock, g.lds_bytes, props);
-  VecArgs v;
-  memset(&v, 0, sizeof(v));
-  v.plan = d_plan;
-  v.kp = kp;
-  v.slabs = nullptr;
-  v.entry_count = g.out_entry_count;
-  v.rep = g.rep;
-  v.run_if = nullptr;
-  v.bh_cap_log2 = g.cap_log2;
+  VecArgs v = bh_vec_args(g, d_plan, kp, nullptr);
   AsyncScratch scratch(s);
   BhFoldArgs fold;
   WordLayout wl;

@@ -5,15 +5,11 @@
 
 namespace hdk {
 
-// kernel name of the launch when the LDS open-addressing strategy takes the plan, else nullptr
-const char* bh_lds_kernel_name(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko);
-// enqueues the scan (which folds its groups into GROUPBY_BUF[0] itself); *launched = false: not this strategy's plan
-int32_t launch_bh_lds(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
-                      const hdk_hip_device_properties* props, hipStream_t s, bool* launched);
+struct BhGeom;  // scan_bh_decl.h
 
 // the open-addressing interpreter ARMED behind another strategy's passes: runs only when *run_if == 1 (scan_agg.hip: the sliced
-// join of a baseline-hash plan); folds into GROUPBY_BUF[0] itself
-int32_t launch_bh_vec_armed(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
+// join of a baseline-hash plan); folds into GROUPBY_BUF[0] itself.  `g`: the geometry its route was matched with (route.h)
+int32_t launch_bh_vec_armed(const BhGeom& g, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
                             const hdk_hip_device_properties* props, hipStream_t s, const uint32_t* run_if);
 // slabs of a DENSE internal table ([slab][entry][word], agg_common.h's slab words: NULL-count words already hold the non-NULL
 // counts) folded into the plan's open-addressing table: internal entry i is the group of key key_lo + i (or the NULL key)
@@ -30,14 +26,5 @@ struct BhDenseFold {
   int64_t null_key;
 };
 int32_t launch_bh_fold_dense(const BhDenseFold& fold, const hdk_hip_plan* d_plan, const KernParams& kp, hipStream_t s);
-// scan_agg.hip: a baseline-hash plan behind the sliced join (internal dense table + hdk_bh_fold_dense)
-const char* baseline_sliced_join_names(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props);
-int32_t launch_baseline_sliced_join(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
-                                    const hdk_hip_device_properties* props, hipStream_t s, bool* launched);
-
-// scan_bh_packed.hip: the packed form (scan_bh_packed.h), tried first
-const char* bh_packed_kernel_name(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko);
-int32_t launch_bh_packed(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
-                         const hdk_hip_device_properties* props, hipStream_t s, bool* launched);
 
 }  // namespace hdk

@@ -331,22 +331,30 @@ static int32_t launch_bh_dense_part(const hdk_hip_plan* d_plan, const KernParams
   return HDK_HIP_OK;
 }
 
-const char* bh_packed_kernel_name(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko) {
-  BhPackedArgs a;
-  int kw, vw, block;
-  uint32_t lds;
-  if (match_bh_packed(p, ko, &a, &kw, &vw, &block, &lds)) {
-    if (bh_plain(a, kw, vw)) return a.dense ? "hdk_scan_agg_bh_dense_plain,hdk_bh_fold_slabs" : "hdk_scan_agg_bh_packed_plain,hdk_bh_fold_slabs";
-    return a.dense ? "hdk_scan_agg_bh_dense,hdk_bh_fold_slabs" : "hdk_scan_agg_bh_packed,hdk_bh_fold_slabs";
+// what a route of this file carries: the argument block and the geometry of the matcher that won
+struct BhPackedRoute { BhPackedArgs a; int kw, vw, block; uint32_t lds; };
+struct BhDensePartRoute { BhDensePartArgs g; BhDensePartLayout l; };
+struct BhPartRoute { BhPackedArgs a; BhPartLayout l; };
+
+bool route_bh_packed(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, RouteSet refused, LaunchRoute* r) {
+  BhPackedRoute& pk = r->as<BhPackedRoute>();
+  if (match_bh_packed(p, ko, &pk.a, &pk.kw, &pk.vw, &pk.block, &pk.lds)) {
+    r->kind = bh_plain(pk.a, pk.kw, pk.vw) ? (pk.a.dense ? ROUTE_BH_DENSE_PLAIN : ROUTE_BH_PACKED_PLAIN) : (pk.a.dense ? ROUTE_BH_DENSE : ROUTE_BH_PACKED);
+    return !route_refused(refused, r->kind);
   }
   // several argument or key columns, and one-argument tables that fit LDS at 12 bytes an entry but not at 24: scan_bhm.hip
-  if (const char* m = bhm_kernel_name(p, ko)) return m;
-  BhDensePartArgs dg;
-  BhDensePartLayout dl;
-  if (match_bh_dense_part(p, ko, &dg, &dl)) return "hdk_bh_dscatter,hdk_bh_daggregate";
-  BhPartLayout l;
-  if (match_bh_partitioned(p, ko, &a, &l)) return "hdk_bh_scatter,hdk_bh_aggregate";
-  return nullptr;
+  if (route_bhm(p, ko, refused, r)) return true;
+  BhDensePartRoute& dp = r->as<BhDensePartRoute>();
+  if (match_bh_dense_part(p, ko, &dp.g, &dp.l)) {
+    r->kind = ROUTE_BH_DENSE_PART;
+    return !route_refused(refused, r->kind);
+  }
+  BhPartRoute& bp = r->as<BhPartRoute>();
+  if (match_bh_partitioned(p, ko, &bp.a, &bp.l)) {
+    r->kind = ROUTE_BH_PARTITIONED;
+    return !route_refused(refused, r->kind);
+  }
+  return false;
 }
 
 static int32_t launch_bh_partitioned(const hdk_hip_plan* d_plan, const KernParams& kp, BhPackedArgs& a, const BhPartLayout& l,
@@ -380,22 +388,16 @@ static int32_t launch_bh_partitioned(const hdk_hip_plan* d_plan, const KernParam
   return HDK_HIP_OK;
 }
 
-int32_t launch_bh_packed(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
-                         const hdk_hip_device_properties* props, hipStream_t s, bool* launched) {
+int32_t launch_bh_packed(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
+                         const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, hipStream_t s, bool* launched) {
   *launched = false;
-  BhPackedArgs a;
-  int kw, vw, block;
-  uint32_t lds;
-  if (!match_bh_packed(plan, ko, &a, &kw, &vw, &block, &lds)) {
-    int32_t st = launch_bhm(plan, d_plan, kp, ko, props, s, launched);
-    if (st || *launched) return st;
-    BhDensePartArgs dg;
-    BhDensePartLayout dl;
-    if (match_bh_dense_part(plan, ko, &dg, &dl)) return launch_bh_dense_part(d_plan, kp, dg, dl, props, s, launched);
-    BhPartLayout l;
-    if (match_bh_partitioned(plan, ko, &a, &l)) return launch_bh_partitioned(d_plan, kp, a, l, props, s, launched);
-    return HDK_HIP_OK;
-  }
+  if (route_family(r.kind) == FAM_BHM) return launch_bhm(r, plan, d_plan, kp, ko, props, s, launched);
+  if (r.kind == ROUTE_BH_DENSE_PART) return launch_bh_dense_part(d_plan, kp, r.as<BhDensePartRoute>().g, r.as<BhDensePartRoute>().l, props, s, launched);
+  if (r.kind == ROUTE_BH_PARTITIONED) return launch_bh_partitioned(d_plan, kp, r.as<BhPartRoute>().a, r.as<BhPartRoute>().l, props, s, launched);
+  BhPackedRoute& pk = r.as<BhPackedRoute>();
+  BhPackedArgs& a = pk.a;
+  const int kw = pk.kw, vw = pk.vw, block = pk.block;
+  const uint32_t lds = pk.lds;
   a.plan = d_plan;
   a.kp = kp;
   const void* k = bh_plain(a, kw, vw) ? bh_plain_kernel(a.dense != 0, kw, vw, block)

@@ -599,19 +599,23 @@ static const void* bhm_aggregate_kernel(const BhmArgs& a, const BhmGeom& g, int 
   return tw == 2 ? bhm_aggregate_dynamic<2>(g.ns) : bhm_aggregate_dynamic<4>(g.ns);
 }
 
-const char* bhm_kernel_name(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko) {
-  BhmArgs a;
-  BhmGeom g;
-  if (!match_bhm(p, ko, &a, &g)) {
-    BhmPartArgs pg;
-    BhmPartLayout l;
-    if (match_bhm_part(p, ko, &pg, &g, &l)) {
-      return g.perfect ? "hdk_bhm_scatter,hdk_bhm_aggregate,hdk_bhm_reduce_slabs,hdk_finalize"
-                       : "hdk_bhm_scatter,hdk_bhm_aggregate,hdk_bhm_reduce_slabs,hdk_bhm_fold";  // (behind hdk_bhm_part_sample, _layout)
-    }
-    return nullptr;
+// what a route of this family carries: the argument block and the geometry of the matcher that won
+struct BhmRoute { BhmArgs a; BhmGeom g; };
+struct BhmPartRoute { BhmPartArgs pg; BhmGeom g; BhmPartLayout l; };
+
+// ONE pass when the dense table fits a block's LDS; else -- only then -- the two passes
+bool route_bhm(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, RouteSet refused, LaunchRoute* r) {
+  BhmRoute& one = r->as<BhmRoute>();
+  if (match_bhm(p, ko, &one.a, &one.g)) {
+    r->kind = one.g.perfect ? ROUTE_BHM_PERFECT : ROUTE_BHM;
+    return !route_refused(refused, r->kind);
   }
-  return g.perfect ? "hdk_scan_agg_bhm,hdk_bhm_reduce_slabs,hdk_finalize" : "hdk_scan_agg_bhm,hdk_bhm_reduce_slabs,hdk_bhm_fold";
+  BhmPartRoute& two = r->as<BhmPartRoute>();
+  if (match_bhm_part(p, ko, &two.pg, &two.g, &two.l)) {
+    r->kind = two.g.perfect ? ROUTE_BHM_PART_PERFECT : ROUTE_BHM_PART;
+    return !route_refused(refused, r->kind);
+  }
+  return false;
 }
 
 // the fold of `fold_count` slabs of the dense table (internal entry i = key_lo + i ...) into the plan's output, and the armed fallback
@@ -652,7 +656,7 @@ static int32_t launch_bhm_folds(const hdk_hip_plan* plan, const hdk_hip_plan* d_
     return HDK_HIP_OK;
   }
   // armed: runs only when the flag says the statistics did not hold (the folds skipped then)
-  return launch_scan_global_armed(plan, d_plan, kp, ko, props, s, a.flag);
+  return launch_scan_global_armed(plan, d_plan, kp, props, s, a.flag);
 }
 
 static int32_t launch_bhm_part(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
@@ -727,17 +731,15 @@ static int32_t launch_bhm_part(const hdk_hip_plan* plan, const hdk_hip_plan* d_p
   return HDK_HIP_OK;
 }
 
-int32_t launch_bhm(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
+int32_t launch_bhm(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
                    const hdk_hip_device_properties* props, hipStream_t s, bool* launched) {
   *launched = false;
-  BhmArgs a;
-  BhmGeom g;
-  if (!match_bhm(plan, ko, &a, &g)) {
-    BhmPartArgs pg;
-    BhmPartLayout l;
-    if (match_bhm_part(plan, ko, &pg, &g, &l)) return launch_bhm_part(plan, d_plan, kp, ko, props, s, pg, g, l, launched);
-    return HDK_HIP_OK;
+  if (r.kind == ROUTE_BHM_PART || r.kind == ROUTE_BHM_PART_PERFECT) {
+    BhmPartRoute& two = r.as<BhmPartRoute>();
+    return launch_bhm_part(plan, d_plan, kp, ko, props, s, two.pg, two.g, two.l, launched);
   }
+  BhmArgs& a = r.as<BhmRoute>().a;
+  const BhmGeom& g = r.as<BhmRoute>().g;
   bool is_static;
   const void* k = bhm_kernel(a, g, &is_static);
   if (a.lds_bytes > (48u << 10)) {

@@ -88,55 +88,49 @@ static bool project_one_pass(const hdk_hip_kernel_options* ko, const ProjFastArg
   return ko && ko->total_rows && hdk_sw(SW_PROJECT_ONE_PASS) && !(pf && pf->join);
 }
 
-uint32_t project_grid(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props) {
-  // a caller's grid is the caller's (include/hdk_hip.h: 0 => library default): the two passes and the interpreters all
-  // stride by gridDim.x.  choose_shape keeps such a grid without asking here; this keeps the answer the same for any other
-  // caller.  (The one-pass kernel has its resident grid either way: its tickets need co-residency.)
-  if (ko && ko->grid_dim_x) return ko->grid_dim_x;
-  const bool scalar = (ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_SCALAR)) || needs_join_loops(p);
+// Always routes: the two-pass filter/project kernels (the one-pass kernel in front of them behind its switch), else one of the plan
+// interpreters.  The grid is the resident grid of the kernel that runs, unless the caller gave one (0 => library default): all of
+// them stride by gridDim.x.  (The one-pass kernel has its resident grid either way: its tickets need co-residency.)
+struct ProjInterpreter { const void* k; int block; };
+void route_project(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, LaunchRoute* r) {
   const void* k;
   int block;
-  ProjFastArgs pf;
+  ProjFastArgs& pf = r->as<ProjFastArgs>();
   if (!launch_forces_generic(ko) && match_project_fast(p, &pf)) {
+    r->kind = project_one_pass(ko, &pf) ? ROUTE_PROJECT_FAST_ONE_PASS : ROUTE_PROJECT_FAST;
     k = reinterpret_cast<const void*>(hdk_scan_project_direct);
     block = kProjFastBlock;
+  } else if (needs_join_loops(p) || (ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_SCALAR))) {
+    r->kind = ROUTE_PROJECT_SCALAR;
+    k = reinterpret_cast<const void*>(hdk_scan_project_scalar);
+    block = kProjBlock;
+  } else if (p->num_joins) {
+    r->kind = plan_has_keyed_join(p) ? ROUTE_PROJECT_KEYED : ROUTE_PROJECT_JOIN;
+    k = plan_has_keyed_join(p) ? reinterpret_cast<const void*>(hdk_scan_project_keyed) : reinterpret_cast<const void*>(hdk_scan_project_join);
+    block = kProjBlockJoin;
   } else {
-    k = scalar ? reinterpret_cast<const void*>(hdk_scan_project_scalar)
-               : (p->num_joins ? (plan_has_keyed_join(p) ? reinterpret_cast<const void*>(hdk_scan_project_keyed)
-                                                         : reinterpret_cast<const void*>(hdk_scan_project_join))
-                               : reinterpret_cast<const void*>(hdk_scan_project));
-    block = scalar ? kProjBlock : (p->num_joins ? kProjBlockJoin : kProjBlockPlain);
+    r->kind = ROUTE_PROJECT;
+    k = reinterpret_cast<const void*>(hdk_scan_project);
+    block = kProjBlockPlain;
   }
-  return resident_grid(k, block, 0, props);
+  if (!(ko && ko->grid_dim_x)) r->shape.grid = resident_grid(k, block, 0, props);
+  if (r->kind != ROUTE_PROJECT_FAST && r->kind != ROUTE_PROJECT_FAST_ONE_PASS) r->as<ProjInterpreter>() = {k, block};
 }
 
-void project_describe(const hdk_hip_plan* plan, const hdk_hip_kernel_options* ko, char* out, size_t out_len) {
-  ProjFastArgs pf;
-  if (!launch_forces_generic(ko) && match_project_fast(plan, &pf)) {
-    snprintf(out, out_len, "%shdk_scan_project_count,hdk_scan_project_offsets,hdk_scan_project_dense,hdk_scan_project_direct",
-             project_one_pass(ko, &pf) ? "hdk_scan_project_stream," : "");
-  } else {
-    snprintf(out, out_len, "%s", needs_join_loops(plan) ? "hdk_scan_project_scalar"
-                                 : plan->num_joins     ? (plan_has_keyed_join(plan) ? "hdk_scan_project_keyed" : "hdk_scan_project_join")
-                                                       : "hdk_scan_project");
-  }
-}
-
-int32_t launch_project(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
-                       const hdk_hip_kernel_options* ko, const LaunchShape& shape, const hdk_hip_device_properties* props,
-                       hipStream_t s) {
+int32_t launch_project(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
+                       const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, hipStream_t s) {
+  const LaunchShape& shape = r.shape;
   ProjArgs pa;
   pa.plan = d_plan;
   pa.kp = kp;
   pa.entry_count = plan->entry_count;
-  ProjFastArgs pf;
-  const bool generic = ko && (ko->flags & (HDK_HIP_LAUNCH_FORCE_GENERIC | HDK_HIP_LAUNCH_FORCE_SCALAR));
-  if (!generic && match_project_fast(plan, &pf)) {
+  if (r.kind == ROUTE_PROJECT_FAST || r.kind == ROUTE_PROJECT_FAST_ONE_PASS) {
+    ProjFastArgs& pf = r.as<ProjFastArgs>();
     pf.kp = kp;
     // ---- one pass (decoupled look-back over batches of tiles), the two passes armed behind it ----------------------
     AsyncScratch status_mem(s);
     bool streamed = false;
-    if (project_one_pass(ko, &pf)) {
+    if (r.kind == ROUTE_PROJECT_FAST_ONE_PASS) {
       // a status word per batch: the stated rows in full tiles, plus one ragged tile per fragment -- 64 K of them
       // (the kernel counts the real tiles and hands the launch to the two passes if they do not fit)
       uint64_t slack = 65536;
@@ -204,14 +198,9 @@ int32_t launch_project(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, con
       hipLaunchKernelGGL(hdk_scan_project_direct, dim3(shape.grid), dim3(kProjFastBlock), 0, s, pf);
     }
     HDK_HIP_CHECK(hipGetLastError());
-  } else if (needs_join_loops(plan) || (ko && (ko->flags & HDK_HIP_LAUNCH_FORCE_SCALAR))) {
-    hipLaunchKernelGGL(hdk_scan_project_scalar, dim3(shape.grid), dim3(kProjBlock), 0, s, pa);
-  } else if (plan->num_joins && plan_has_keyed_join(plan)) {
-    hipLaunchKernelGGL(hdk_scan_project_keyed, dim3(shape.grid), dim3(kProjBlockJoin), 0, s, pa);
-  } else if (plan->num_joins) {
-    hipLaunchKernelGGL(hdk_scan_project_join, dim3(shape.grid), dim3(kProjBlockJoin), 0, s, pa);
-  } else {
-    hipLaunchKernelGGL(hdk_scan_project, dim3(shape.grid), dim3(kProjBlockPlain), 0, s, pa);
+  } else {  // the interpreter route_project chose
+    void* kargs[] = {&pa};
+    HDK_HIP_CHECK(hipLaunchKernel(r.as<ProjInterpreter>().k, dim3(shape.grid), dim3(r.as<ProjInterpreter>().block), kargs, 0, s));
   }
   HDK_HIP_CHECK(hipGetLastError());
   return HDK_HIP_OK;

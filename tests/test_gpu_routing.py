@@ -69,3 +69,18 @@ def test_assumed_device_routes_the_star_schema_shapes_like_this_device():
         cp = R._fused(compile_query(st, q))
         for rows in (R.BIG, 1_000_000):
             assert _names_on(cp, 0, rows) == _names_on(cp, R.ASSUMED_MI355X, rows), (q, rows)
+
+
+def test_workspaces_are_the_recorded_ones():
+    """`hdk_hip_workspace_size` on the device for every plan of the routing corpus (tests/routing_corpus.py) at one billion rows,
+    no flag, no switch: the sizes recorded before the routing step existed.  For an LDS-strategy plan the size is plan region +
+    grid x slab words x 8, so a grid that is sized for another kernel than before shows.  (Rows under forced flags are not in
+    the table: a forced-generic launch is now sized for the kernel it runs.)  Nothing is allocated but the plans."""
+    import json
+    import routing_corpus as RC
+    with open(RC.GOLDEN_WORKSPACES) as f:
+        want = json.load(f)
+    got = RC.workspace_sizes(RC.corpus(), 0)
+    assert list(got) == list(want)
+    wrong = {pid: (got[pid], want[pid]) for pid in want if got[pid] != want[pid]}
+    assert not wrong, wrong

@@ -2,9 +2,12 @@
 
 Kernel routing (the `match_*` functions of hdk_amd/csrc) is host arithmetic over the plan, the kernel options and a few
 device numbers; `hdk_hip_describe_launch` answers it for an assumed MI355X (`HDK_HIP_DEVICE_ASSUMED_MI355X`) without touching a
-device.  The GPU suite asserts the same names on the device (and `test_gpu_abi_negative.py` that the assumed numbers are the
-device's); here the driver's per-round CPU run sees a routing regression -- a benchmark shape falling back to an
-interpreter or to global atomics -- without waiting for a GPU.  Tables are small (the statistics and NDV bounds are what
+device.  The names are the launch's own decision: `hdk_hip_launch` and `hdk_hip_describe_launch` take the same route from the
+same routing step (csrc/route.h) and the names are a table over its enumerator, so a wrong edit of the routing shows here.
+The GPU suite asserts the same names on the device (and `test_gpu_abi_negative.py` that the assumed numbers are the
+device's); tests/test_routing_corpus.py pins a wider corpus under every flag and switch; here the driver's per-round CPU run
+sees a routing regression -- a benchmark shape falling back to an interpreter or to global atomics -- without waiting for a
+GPU.  Tables are small (the statistics and NDV bounds are what
 routing reads); `total_rows` is passed as the BASELINE size.
 """
 import ctypes as C
