@@ -17,6 +17,8 @@ MAX_EXPR_STEPS = 3
 MAX_FILTER_OPS = 16
 MAX_ORDER_ENTRIES = 8
 MAX_HAVING_LEAVES = 8
+MAX_GROUP_KEYS = 8
+MAX_GROUP_OUTS = 16
 SORT_NO_SELECT = 1  # hdk_hip_sort_columns flags
 F_AND, F_OR, F_NOT = 64, 65, 66
 PLAN_ABI = 4
@@ -162,6 +164,14 @@ class HavingLeaf(C.Structure):
                 ("cmp_fp", C.c_uint8), ("lhs_is_fp", C.c_uint8), ("lhs_nullable", C.c_uint8), ("rhs_is_fp", C.c_uint8),
                 ("rhs_nullable", C.c_uint8), ("pad_", C.c_uint8), ("lhs_null_bits", C.c_int64),
                 ("rhs_null_bits", C.c_int64), ("rhs_lit", C.c_int64)]
+
+
+class GroupOut(C.Structure):
+    """hdk_hip_group_out: one output of a GROUP BY over dense result columns (hdk_hip_group_columns): ID of a key column,
+    COUNT (col < 0: the rows of the run), SUM, MIN or MAX of column `col`, whose word is NULL when the out is nullable and
+    the word equals null_bits."""
+    _fields_ = [("col", C.c_int32), ("kind", C.c_uint8), ("is_fp", C.c_uint8), ("nullable", C.c_uint8), ("pad_", C.c_uint8),
+                ("null_bits", C.c_int64)]
 
 
 class KernelOptions(C.Structure):

@@ -79,6 +79,9 @@ SIGNATURES = {
     "hdk_hip_filter_columns_workspace_bytes": (sz, [C.c_uint64]),
     "hdk_hip_filter_columns": (i32, [v, C.c_uint64, i32, C.c_uint64, C.POINTER(A.HavingLeaf), i32, v, i32, v, C.c_uint64, v, v,
                                      v, sz, i32, v]),
+    "hdk_hip_group_columns_workspace_bytes": (sz, [C.c_uint64, i32]),
+    "hdk_hip_group_columns": (i32, [v, C.c_uint64, i32, C.c_uint64, C.POINTER(i32), i32, C.POINTER(A.GroupOut), i32, v,
+                                    C.c_uint64, v, v, sz, i32, v]),
     "hdk_hip_exchange_shape_for": (i32, [C.POINTER(A.Plan), C.POINTER(A.KernelOptions), i32, u32, i32,
                                          C.POINTER(A.ExchangeShape)]),
     "hdk_hip_scatter_to_owners": (i32, [C.POINTER(A.Plan), C.POINTER(v), C.POINTER(A.KernelOptions),
@@ -112,6 +115,7 @@ EXTRA_SIGNATURES = {
     "hdk_hip_sizeof_join": (sz, []),
     "hdk_hip_sizeof_device_properties": (sz, []),
     "hdk_hip_sizeof_kernel_options": (sz, []),
+    "hdk_hip_sizeof_group_out": (sz, []),
 }
 
 

@@ -173,7 +173,7 @@ extern "C" int32_t hdk_hip_set_interrupt(int32_t device_id, int32_t value) {
 extern "C" {
 
 const char* hdk_hip_last_error(void) { return tl_error; }
-int32_t hdk_hip_version(void) { return 1003; }
+int32_t hdk_hip_version(void) { return 1004; }
 
 int32_t hdk_hip_mgr_get_device_count(int32_t* count) {
   HDK_REQUIRE(count, "count is NULL");
@@ -472,5 +472,6 @@ size_t hdk_hip_sizeof_qual(void) { return sizeof(hdk_hip_qual); }
 size_t hdk_hip_sizeof_join(void) { return sizeof(hdk_hip_join); }
 size_t hdk_hip_sizeof_device_properties(void) { return sizeof(hdk_hip_device_properties); }
 size_t hdk_hip_sizeof_kernel_options(void) { return sizeof(hdk_hip_kernel_options); }
+size_t hdk_hip_sizeof_group_out(void) { return sizeof(hdk_hip_group_out); }
 
 }  // extern "C"

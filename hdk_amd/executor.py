@@ -23,8 +23,9 @@ from . import result_set
 from ._lib import HdkHipError, check, lib, sync_switches
 from .hip_mgr import DeviceBuffer, HipMgr
 from .ir import QueryMustRunOnCpu, QueryUnit
-from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, CompiledPlan, Having, columnar_init_vals, compact_init_vals,
-                   compile_query, eff_key_count, resolve_having, resolve_order_by)
+from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, GROUP_KINDS, ColumnDesc, CompiledPlan, Having, columnar_init_vals,
+                   compact_init_vals, compile_query, describe_columns, eff_key_count, has_count_distinct, regroup_columns,
+                   resolve_having, resolve_having_columns, resolve_order_by, split_count_distinct)
 from .storage import ArrowStorage
 
 
@@ -132,22 +133,46 @@ def sized_columns(mgr, device_id, num_targets, worst_rows, call, one_call_bytes,
 class DeviceColumns:
     """Dense result columns in device memory: what hdk_hip_columnarize_result made of a group-by buffer (the device form
     of the reference's ColumnarResults for a ResultSet that lives in HBM).  One 8-byte column per target, rows in entry
-    order -- the order ExecutionResult.to_columns() gives.  Owns its device block until free()."""
+    order -- the order ExecutionResult.to_columns() gives.  Owns its device block until free().
+    A result made from a plan reads its columns' description from the plan (result_set.dense_column_null, cp.out_cols).
+    A regrouped result (group_by) no longer has the plan's schema and carries `schema`, one plan.ColumnDesc per column;
+    `compiled` is then the plan it descends from, kept for reference only."""
 
     def __init__(self, cp: CompiledPlan, mgr: HipMgr, device_id: int, block: Optional[DeviceBuffer], capacity: int,
-                 num_rows: int, error_code: int = 0):
+                 num_rows: int, error_code: int = 0, schema: Optional[List[ColumnDesc]] = None):
         self.compiled, self.mgr, self.device_id = cp, mgr, device_id
         self.block, self.capacity, self.num_rows, self.error_code = block, int(capacity), int(num_rows), error_code
+        self.schema = list(schema) if schema is not None else None
+
+    @property
+    def num_cols(self) -> int:
+        return len(self.schema) if self.schema is not None else int(self.compiled.plan.num_targets)
+
+    def columns(self) -> List[ColumnDesc]:
+        """One ColumnDesc per column: its own for a regrouped result, derived from the plan otherwise."""
+        return list(self.schema) if self.schema is not None else describe_columns(self.compiled)
+
+    def _like(self, block, capacity, num_rows) -> "DeviceColumns":
+        return DeviceColumns(self.compiled, self.mgr, self.device_id, block, capacity, num_rows, self.error_code, self.schema)
+
+    def _column_null(self, t: int):
+        """(is_fp, nullable, null_bits) of column t"""
+        if self.schema is None:
+            return result_set.dense_column_null(self.compiled, t)
+        d = self.schema[t]
+        return d.is_fp, d.nullable, d.null_bits
 
     def device_ptr(self, target_idx: int) -> int:
         """Device address of target `target_idx`'s column: num_rows 8-byte values."""
-        if not 0 <= target_idx < self.compiled.plan.num_targets:
+        if not 0 <= target_idx < self.num_cols:
             raise IndexError(target_idx)
         if self.block is None or not self.block.ptr:
             raise ValueError("the columns have been freed")
         return self.block.ptr + target_idx * self.capacity * 8
 
     def _is_fp(self, target_idx: int) -> bool:
+        if self.schema is not None:
+            return bool(self.schema[target_idx].is_fp)
         tg = self.compiled.plan.targets[target_idx]
         if tg.agg == A.AGG_ID:
             return bool(self.compiled.key_types[tg.key_idx].is_fp)
@@ -156,7 +181,7 @@ class DeviceColumns:
     def to_host(self) -> List[np.ndarray]:
         """One numpy array of num_rows values per target: float64 for fp values (AVG, fp aggregates, fp keys), int64
         for everything else.  NULLs stay in band (the slot's sentinel sign-extended; NULL_DOUBLE for fp values)."""
-        nt = self.compiled.plan.num_targets
+        nt = self.num_cols
         n = self.num_rows
         if n == 0:
             return [np.empty(0, dtype=np.float64 if self._is_fp(t) else np.int64) for t in range(nt)]
@@ -168,9 +193,14 @@ class DeviceColumns:
         return [c.view(np.float64) if self._is_fp(t) else c for t, c in enumerate(cols)]
 
     def to_columns(self):
-        return result_set.dense_to_columns(self.compiled, [c.view(np.int64) for c in self.to_host()])
+        dense = [c.view(np.int64) for c in self.to_host()]
+        if self.schema is not None:
+            return result_set.described_to_columns(self.schema, dense)
+        return result_set.dense_to_columns(self.compiled, dense)
 
     def to_arrow(self):
+        if self.schema is not None:
+            return result_set.described_to_arrow(self.schema, self.to_columns())
         return result_set.columns_to_arrow(self.compiled, self.to_columns())
 
     def row_count(self):
@@ -185,18 +215,17 @@ class DeviceColumns:
         where a LIMIT would select the candidates first (HDK_HIP_SORT_NO_SELECT)."""
         if (limit is not None and limit < 0) or offset < 0:
             raise ValueError("limit and offset must not be negative")
-        cp = self.compiled
-        nt = int(cp.plan.num_targets)
+        nt = self.num_cols
         entries = [e if isinstance(e, tuple) else None for e in order_by]
         if any(e is None for e in entries):
-            entries = resolve_order_by(cp.out_cols, nt, list(order_by))
+            entries = resolve_order_by(self.schema if self.schema is not None else self.compiled.out_cols, nt, list(order_by))
         n = self.num_rows
         after = max(n - int(offset), 0)
         out_rows = after if not limit else min(int(limit), after)
         if limit == 0:  # (LIMIT 0 is no row; the C ABI's 0 means "no limit")
             out_rows = 0
         if out_rows == 0:
-            return DeviceColumns(cp, self.mgr, self.device_id, None, 0, 0, self.error_code)
+            return self._like(None, 0, 0)
         if self.block is None or not self.block.ptr:
             raise ValueError("the columns have been freed")
         block = self.mgr.alloc(nt * out_rows * 8, self.device_id)
@@ -208,7 +237,7 @@ class DeviceColumns:
             else:
                 arr = (A.OrderEntry * len(entries))()
                 for i, (t, desc, nulls_first) in enumerate(entries):
-                    is_fp, nullable, null_bits = result_set.dense_column_null(cp, t)
+                    is_fp, nullable, null_bits = self._column_null(t)
                     arr[i] = A.OrderEntry(t, int(desc), int(nulls_first), int(is_fp), int(nullable), A.to_i64(null_bits))
                 check(lib().hdk_hip_sort_columns(self.block.ptr, self.capacity, nt, n, arr, len(entries), int(offset),
                                                  out_rows if limit else 0, A.SORT_NO_SELECT if no_select else 0, block.ptr,
@@ -217,7 +246,7 @@ class DeviceColumns:
         except Exception:
             block.free()
             raise
-        return DeviceColumns(cp, self.mgr, self.device_id, block, out_rows, out_rows, self.error_code)
+        return self._like(block, out_rows, out_rows)
 
     FILTER_ONE_CALL_BYTES = ONE_CALL_BYTES
 
@@ -228,15 +257,18 @@ class DeviceColumns:
         plan.Having.  Sizing as fetch_columns(): up to 64 MiB of worst-case output one call writes into a block of
         num_rows rows per column; above that the passing rows are counted first (out_cols = NULL) and the block holds
         exactly those.  One stream synchronisation per call, to read row_count back."""
-        cp = self.compiled
         if not isinstance(having, Having):
-            having = resolve_having(cp, list(having) if isinstance(having, (list, tuple)) else [having])
-        nt = int(cp.plan.num_targets)
+            conds = list(having) if isinstance(having, (list, tuple)) else [having]
+            if self.schema is not None:
+                having = resolve_having_columns(self.schema, len(self.schema), self._column_null, conds)
+            else:
+                having = resolve_having(self.compiled, conds)
+        nt = self.num_cols
         n = self.num_rows
         if n == 0 or having is None:
             if having is None and n:
                 return self.sort([])  # no predicate: every row, copied
-            return DeviceColumns(cp, self.mgr, self.device_id, None, 0, 0, self.error_code)
+            return self._like(None, 0, 0)
         if self.block is None or not self.block.ptr:
             raise ValueError("the columns have been freed")
         leaves = (A.HavingLeaf * len(having.leaves))()
@@ -253,7 +285,45 @@ class DeviceColumns:
 
         block, capacity, rows = sized_columns(self.mgr, self.device_id, nt, n, call, self.FILTER_ONE_CALL_BYTES,
                                               drop_empty=True)
-        return DeviceColumns(cp, self.mgr, self.device_id, block, capacity, rows, self.error_code)
+        return self._like(block, capacity, rows)
+
+    GROUP_ONE_CALL_BYTES = ONE_CALL_BYTES
+
+    def group_by(self, keys, outs, presorted: bool = False) -> "DeviceColumns":
+        """GROUP BY `keys` over these columns on the device (hdk_hip_group_columns; the device form of the reference's
+        merge of partial results, QE/ResultSetReduction.cpp reduceOneSlot) -> a new DeviceColumns with one row per
+        distinct key and one column per out, which carries its own schema; this object stays valid.  `keys`: columns by
+        index or name.  `outs`: (kind, target, name) with kind in id / count / sum / min / max, target None for COUNT(*)
+        and name None for a default (plan.regroup_columns has the rules for type and nullability).  The library groups
+        ADJACENT rows: unless `presorted` says that rows with equal keys already are, a copy sorted by the keys is made
+        first (hdk_hip_sort_columns, no limit) and freed afterwards.  Rows come out in that order: ascending by the
+        keys, NULLs last.  Sizing as filter(): up to 64 MiB of worst-case output in one call, else count first."""
+        key_cols, spec, descs = regroup_columns(self.columns(), keys, outs)
+        out = DeviceColumns(self.compiled, self.mgr, self.device_id, None, 0, 0, self.error_code, descs)
+        n = self.num_rows
+        if n == 0:
+            return out
+        if self.block is None or not self.block.ptr:
+            raise ValueError("the columns have been freed")
+        src = self if presorted else self.sort([(k, False, False) for k in key_cols])
+        try:
+            nc = self.num_cols
+            kc = (C.c_int32 * len(key_cols))(*key_cols)
+            arr = (A.GroupOut * len(spec))()
+            for j, (kind, t) in enumerate(spec):
+                is_fp, nullable, null_bits = self._column_null(t) if t >= 0 else (False, False, 0)
+                arr[j] = A.GroupOut(t, GROUP_KINDS[kind], int(is_fp), int(nullable), 0, A.to_i64(null_bits))
+
+            def call(out_ptr, capacity, row_count_ptr):
+                check(lib().hdk_hip_group_columns(src.block.ptr, src.capacity, nc, n, kc, len(key_cols), arr, len(spec), out_ptr,
+                                                  capacity, row_count_ptr, None, 0, self.device_id, None))
+
+            out.block, out.capacity, out.num_rows = sized_columns(self.mgr, self.device_id, len(spec), n, call,
+                                                                  self.GROUP_ONE_CALL_BYTES, drop_empty=True)
+        finally:
+            if src is not self:
+                src.free()
+        return out
 
     def free(self):
         if self.block is not None:
@@ -729,6 +799,11 @@ class Executor:
         if result not in ("buffer", "columns"):
             raise ValueError(f"result must be 'buffer' or 'columns', not {result!r}")
         sq = q.query if isinstance(q, CompiledPlan) else q
+        if has_count_distinct(sq):
+            if result == "buffer":
+                raise ValueError("count_distinct needs result='columns': it regroups the dense result columns of an inner "
+                                 "GROUP BY, which no hash-table buffer holds")
+            return self._execute_count_distinct(sq, frag_ids, **kw)
         sorts = bool(sq.order_by) or sq.limit is not None or bool(sq.offset)
         if sorts and result == "buffer":
             raise ValueError("order_by / limit / offset need result='columns': a hash-table buffer has no row order")
@@ -767,3 +842,26 @@ class Executor:
                 q = dataclasses.replace(q, baseline_entry_count=guess)
             finally:
                 step.free()
+
+    def _execute_count_distinct(self, q: QueryUnit, frag_ids=None, **kw) -> DeviceColumns:
+        """COUNT(DISTINCT x) GROUP BY k in two steps (plan.split_count_distinct): the inner unit GROUP BY k, x as an
+        ordinary plan with whatever kernels it is routed to, then DeviceColumns.group_by by k over its dense columns;
+        HAVING and the SortInfo apply to the regrouped columns.  Every intermediate block is handed back."""
+        inner, rg = split_count_distinct(q)
+        cols = self.execute(inner, frag_ids=frag_ids, result="columns", **kw)
+        try:
+            out = cols.group_by(rg.keys, rg.outs)
+        finally:
+            cols.free()
+        if rg.having:
+            try:
+                kept = out.filter(rg.having)
+            finally:
+                out.free()
+            out = kept
+        if not (rg.order_by or rg.limit is not None or rg.offset):
+            return out
+        try:
+            return out.sort(rg.order_by, rg.limit, rg.offset)
+        finally:
+            out.free()

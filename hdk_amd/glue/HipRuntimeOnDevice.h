@@ -227,4 +227,23 @@ inline void filter_columns_on_device(const int64_t* cols, const size_t capacity,
                                workspace_bytes, device_id, nullptr));
 }
 
+// GROUP BY for a result whose dense columns are on the device and sorted by the keys (sort_columns_on_device): the merge of
+// partial results per slot (reduceOneSlot, QueryEngine/ResultSetReduction.cpp) with the _skip_val NULL rules, as a second
+// aggregation step -- a roll-up, SELECT DISTINCT, the outer half of COUNT(DISTINCT).  One row per run of adjacent rows
+// whose words in the `key_cols` are bit-equal, in input order, column j of `outs` at out_cols + j * out_capacity;
+// *row_count_dev (device) always receives the true number of runs, rows at or beyond out_capacity are not written,
+// out_cols == nullptr counts only.  `workspace` comes from the BufferProvider (group_columns_workspace_bytes(num_rows,
+// num_outs) bytes) or is null (the stream's memory pool).  Asynchronous on the device's stream: the host never waits.
+inline size_t group_columns_workspace_bytes(const size_t num_rows, const int num_outs) {
+  return hdk_hip_group_columns_workspace_bytes(static_cast<uint64_t>(num_rows), num_outs);
+}
+inline void group_columns_on_device(const int64_t* cols, const size_t capacity, const int num_cols, const size_t num_rows,
+                                    const int32_t* key_cols, const int num_keys, const hdk_hip_group_out* outs, const int num_outs,
+                                    int64_t* out_cols, const size_t out_capacity, uint64_t* row_count_dev, int8_t* workspace,
+                                    const size_t workspace_bytes, const int device_id) {
+  check(hdk_hip_group_columns(cols, static_cast<uint64_t>(capacity), num_cols, static_cast<uint64_t>(num_rows), key_cols, num_keys,
+                              outs, num_outs, out_cols, static_cast<uint64_t>(out_capacity), row_count_dev, workspace, workspace_bytes,
+                              device_id, nullptr));
+}
+
 }  // namespace hip_rt

@@ -180,7 +180,9 @@ Cond = Union[Cmp, And, Or, Not]
 
 @dataclass(frozen=True)
 class Agg:
-    """Aggregate target: kind in count/sum/min/max/avg/single_value; arg None = COUNT(*)."""
+    """Aggregate target: kind in count/sum/min/max/avg/single_value; arg None = COUNT(*).  kind count_distinct
+    (COUNT(DISTINCT arg)) is valid in a group-by unit run with Executor.execute(result="columns"), which runs it as
+    GROUP BY keys, arg followed by a regroup of the dense columns by the keys (plan.split_count_distinct)."""
     kind: str
     arg: Optional[Expr] = None
     name: Optional[str] = None

@@ -323,6 +323,98 @@ class OutCol:
     scale: int = 0  # decimal scale of the aggregate's argument (values are scaled int64)
 
 
+@dataclass(frozen=True)
+class ColumnDesc:
+    """One dense device column described by itself: what a DeviceColumns that no longer has the schema of a CompiledPlan
+    (DeviceColumns.group_by) carries per column.  is_fp / nullable / null_bits say how the 8-byte words compare and which
+    word is the in-band NULL (hdk_hip_order_entry's fields); type, dictionary and scale say how to_columns() / to_arrow()
+    present them (a string id through its dictionary, a scaled decimal divided by 10 ** scale).  Reads like an OutCol
+    where one is expected (resolve_order_by, resolve_having_columns)."""
+    name: str
+    is_fp: bool
+    nullable: bool
+    null_bits: int
+    type: Type
+    target_idx: int = -1
+    kind: str = "agg"  # 'key' | 'agg', as OutCol
+    agg: str = ""
+    dictionary: Optional[list] = None
+    scale: int = 0
+
+
+def describe_columns(cp: "CompiledPlan") -> List[ColumnDesc]:
+    """The ColumnDesc of every dense column of a plan's result, by target index: result_set.dense_column_null and
+    cp.out_cols restated per column."""
+    from .result_set import dense_column_null
+    res = []
+    for oc in sorted(cp.out_cols, key=lambda c: c.target_idx):
+        is_fp, nullable, null_bits = dense_column_null(cp, oc.target_idx)
+        scaled = oc.kind == "agg" and oc.agg in ("sum", "min", "max", "avg")  # (_column_values scales only these)
+        res.append(ColumnDesc(oc.name, bool(is_fp), bool(nullable), A.to_i64(null_bits), oc.type, oc.target_idx, oc.kind,
+                              oc.agg, oc.dictionary, oc.scale if scaled else 0))
+    return res
+
+
+GROUP_KINDS = {"id": A.AGG_ID, "count": A.AGG_COUNT, "sum": A.AGG_SUM, "min": A.AGG_MIN, "max": A.AGG_MAX}
+
+
+def regroup_columns(cols: List[ColumnDesc], keys, outs) -> Tuple[List[int], List[tuple], List[ColumnDesc]]:
+    """DeviceColumns.group_by's arguments resolved against the columns `cols`: -> (key column indices, [(kind, column
+    or -1)], the ColumnDesc of every output).  `keys`: columns by index or name; `outs`: (kind, target, name) with kind
+    in id / count / sum / min / max, target None for COUNT(*), name None for a default.  ID, MIN and MAX inherit the
+    input's description, SUM its is_fp / nullable / null_bits (an integer sum is an int64, a decimal keeps its scale),
+    COUNT is a non-nullable int64.  A ValueError: an unknown column, no key or out, an ID of a column that is not a
+    key, SUM of a dictionary-encoded column; more keys or outs than the library takes must run on the CPU."""
+    by_name = {c.name: i for i, c in enumerate(cols)}
+
+    def column(t, what):
+        if isinstance(t, str):
+            if t not in by_name:
+                raise ValueError(f"GROUP BY {what} names no column: {t!r}")
+            return by_name[t]
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < len(cols):
+            raise ValueError(f"GROUP BY {what} column index {t!r} outside 0..{len(cols) - 1}")
+        return int(t)
+
+    key_cols = [column(k, "key") for k in keys]
+    outs = list(outs)
+    if not key_cols or not outs:
+        raise ValueError("GROUP BY needs at least one key and one out (SELECT DISTINCT k is outs = [('id', k, None)])")
+    if len(key_cols) > A.MAX_GROUP_KEYS or len(outs) > A.MAX_GROUP_OUTS:
+        raise QueryMustRunOnCpu("more than %d GROUP BY keys or %d outs" % (A.MAX_GROUP_KEYS, A.MAX_GROUP_OUTS))
+    spec, descs = [], []
+    for j, (kind, target, name) in enumerate(outs):
+        if kind not in GROUP_KINDS:
+            raise ValueError(f"GROUP BY out kind {kind!r} (id, count, sum, min or max)")
+        if target is None:
+            if kind != "count":
+                raise ValueError(f"{kind} needs a column")
+            spec.append((kind, -1))
+            descs.append(ColumnDesc(name or f"count_{j}", False, False, 0, Type("int", 8, False), j, "agg", "count"))
+            continue
+        t = column(target, "out")
+        src = cols[t]
+        if kind == "id":
+            if t not in key_cols:
+                raise ValueError(f"GROUP BY out {j} is the ID of column {src.name!r}, which is not a key")
+            d = ColumnDesc(name or src.name, src.is_fp, src.nullable, src.null_bits, src.type, j, "key", "", src.dictionary,
+                           src.scale)
+        elif kind == "count":
+            d = ColumnDesc(name or f"count_{j}", False, False, 0, Type("int", 8, False), j, "agg", "count")
+        elif kind == "sum":
+            if src.dictionary is not None or src.type.kind == "dict":
+                raise ValueError(f"SUM of a dictionary-encoded column ({src.name}): string ids do not add up")
+            ty = src.type if src.is_fp else Type(src.type.kind if src.type.kind == "decimal" else "int", 8, True,
+                                                 src.type.scale)
+            d = ColumnDesc(name or f"sum_{j}", src.is_fp, src.nullable, src.null_bits, ty, j, "agg", "sum", None, src.scale)
+        else:
+            d = ColumnDesc(name or f"{kind}_{j}", src.is_fp, src.nullable, src.null_bits, src.type, j, "agg", kind,
+                           src.dictionary, src.scale)
+        spec.append((kind, t))
+        descs.append(d)
+    return key_cols, spec, descs
+
+
 @dataclass
 class CompiledPlan:
     plan: A.Plan
@@ -716,7 +808,7 @@ def resolve_order_by(out_cols: List["OutCol"], num_targets: int, order_by) -> Li
             if isinstance(e.target, bool) or not 0 <= int(e.target) < num_targets:
                 raise ValueError(f"ORDER BY target index {e.target!r} outside 0..{num_targets - 1}")
             oc = by_idx[int(e.target)]
-        if oc.kind == "key" and oc.dictionary is not None:
+        if oc.dictionary is not None and (oc.kind == "key" or isinstance(oc, ColumnDesc)):  # (a regrouped MIN / MAX of ids too)
             raise QueryMustRunOnCpu(f"ORDER BY a dictionary-encoded key ({oc.name}): id order is not string order")
         res.append((oc.target_idx, bool(e.desc), bool(e.nulls_first)))
     return res
@@ -764,9 +856,17 @@ def resolve_having(cp: CompiledPlan, having) -> Optional[Having]:
     kind = cp.plan.query_kind
     if kind != A.Q_PERFECT_HASH and kind != A.Q_BASELINE_HASH:
         raise QueryMustRunOnCpu("HAVING on a step that is not a group-by: it has no dense device columns")
-    nt = int(cp.plan.num_targets)
-    by_name = {oc.name: oc for oc in cp.out_cols}
-    by_idx = {oc.target_idx: oc for oc in cp.out_cols}
+    return resolve_having_columns(cp.out_cols, int(cp.plan.num_targets), lambda t: dense_column_null(cp, t), having)
+
+
+def resolve_having_columns(out_cols, nt: int, null_of, having) -> Optional[Having]:
+    """resolve_having against any dense columns: `out_cols` describe them the way OutCol does (name, target_idx, type,
+    dictionary, scale -- a ColumnDesc will do) and null_of(t) gives column t's (is_fp, nullable, null_bits)."""
+    having = list(having)
+    if not having:
+        return None
+    by_name = {oc.name: oc for oc in out_cols}
+    by_idx = {oc.target_idx: oc for oc in out_cols}
 
     def target(e: TargetRef) -> int:
         if isinstance(e.target, str):
@@ -793,10 +893,10 @@ def resolve_having(cp: CompiledPlan, having) -> Optional[Having]:
             raise QueryMustRunOnCpu(f"HAVING compares a target with a literal or a target; arithmetic inside a comparison "
                                     f"({c!r}) is outside the fixed kernel library")
         lt = target(lhs)
-        l_fp, l_nullable, l_null = dense_column_null(cp, lt)
+        l_fp, l_nullable, l_null = null_of(lt)
         if isinstance(rhs, TargetRef):
             rt = target(rhs)
-            r_fp, r_nullable, r_null = dense_column_null(cp, rt)
+            r_fp, r_nullable, r_null = null_of(rt)
             return HavingLeaf(lt, cmp, True, rt, 0, bool(l_fp or r_fp), bool(l_fp), bool(l_nullable), A.to_i64(l_null),
                               bool(r_fp), bool(r_nullable), A.to_i64(r_null))
         v = rhs.value
@@ -867,6 +967,9 @@ def _reject_target_refs_outside_having(q: QueryUnit):
 def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
     from .ir import Proj
     _reject_target_refs_outside_having(q)
+    if has_count_distinct(q):
+        raise ValueError("count_distinct is rewritten above compile_query: compile the inner unit of split_count_distinct(q) "
+                         "and regroup its dense columns (Executor.execute(result='columns') does both)")
     if q.limit is not None and q.limit < 0 or q.offset < 0:
         raise ValueError("limit and offset must not be negative")
     if q.targets and all(isinstance(t, Proj) for t in q.targets):
@@ -1297,3 +1400,66 @@ def init_buffer_host(cp: CompiledPlan, entry_count: Optional[int] = None) -> np.
         buf[:, :keys_quads] = kb.view(np.int64)
     buf[:, keys_quads:] = compact_init_vals(cp)[None, :]
     return buf.reshape(-1).copy()
+
+
+# ---------------------------------------------------------------------------------------------
+# COUNT(DISTINCT x) GROUP BY k  =  GROUP BY k, x  followed by  GROUP BY k, COUNT(x) over that result
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class Regroup:
+    """The second step of a unit with count_distinct targets: DeviceColumns.group_by(keys, outs) over the inner unit's
+    dense columns gives the unit's targets in their order under their names; having / order_by / limit / offset are the
+    unit's own and apply to those columns."""
+    keys: List[int]  # inner targets: the unit's group-by keys
+    outs: List[tuple]  # (kind, inner target or None, name) per target of the unit
+    having: list
+    order_by: list
+    limit: Optional[int]
+    offset: int
+
+
+def has_count_distinct(q: QueryUnit) -> bool:
+    return any(isinstance(t, Agg) and t.kind == "count_distinct" for t in q.targets)
+
+
+def split_count_distinct(q: QueryUnit) -> Tuple[QueryUnit, Regroup]:
+    """A group-by unit with Agg("count_distinct", x) targets -> (inner unit, Regroup).  The inner unit has the same table,
+    quals and joins, groups by the unit's keys and x, and projects the keys, x and a partial for every other aggregate;
+    the regroup by the keys turns COUNT(DISTINCT x) into COUNT(x column) -- a NULL x is an inner group of its own and is
+    not counted, as SQL requires --, COUNT into the SUM of the partial counts and keeps SUM, MIN and MAX.  What the two
+    steps cannot express must run on the CPU: two different distinct arguments, avg or single_value beside a distinct
+    aggregate, count_distinct without a group-by."""
+    import dataclasses
+    distinct = [t for t in q.targets if isinstance(t, Agg) and t.kind == "count_distinct"]
+    if not distinct:
+        raise ValueError("the unit has no count_distinct target")
+    if any(t.arg is None for t in distinct):
+        raise ValueError("count_distinct needs an argument")
+    if not q.groupby:
+        raise QueryMustRunOnCpu("count_distinct without a GROUP BY: the regroup step needs a key")
+    arg = distinct[0].arg
+    if any(t.arg != arg for t in distinct):
+        raise QueryMustRunOnCpu("count_distinct over two different arguments: one regroup counts one inner key")
+    nk = len(q.groupby)
+    inner_targets = [KeyRef(i, f"__key{i}") for i in range(nk)] + [KeyRef(nk, "__distinct")]
+    outs = []
+    for ti, t in enumerate(q.targets):
+        if isinstance(t, KeyRef):
+            if not 0 <= t.idx < nk:
+                raise ValueError(f"KeyRef({t.idx}) names no group-by key")
+            src = q.groupby[t.idx]
+            outs.append(("id", t.idx, t.name or (src.name if isinstance(src, ColRef) else f"key{t.idx}")))
+        elif not isinstance(t, Agg):
+            raise QueryMustRunOnCpu("mixing projections and aggregates")
+        elif t.kind == "count_distinct":
+            outs.append(("count", nk, t.name or f"count_distinct_{ti}"))
+        elif t.kind in ("avg", "single_value"):
+            raise QueryMustRunOnCpu(f"{t.kind} beside a count_distinct: its partials do not regroup")
+        elif t.kind in ("count", "sum", "min", "max"):
+            outs.append(("sum" if t.kind == "count" else t.kind, len(inner_targets), t.name or f"{t.kind}_{ti}"))
+            inner_targets.append(Agg(t.kind, t.arg, f"__partial{ti}"))
+        else:
+            raise ValueError(f"unknown aggregate {t.kind!r}")
+    inner = dataclasses.replace(q, groupby=list(q.groupby) + [arg], targets=inner_targets, order_by=[], limit=None, offset=0,
+                                having=[])
+    return inner, Regroup(list(range(nk)), outs, list(q.having), list(q.order_by), q.limit, q.offset)

@@ -295,3 +295,42 @@ def columns_to_arrow(cp: CompiledPlan, cols: Dict[str, list]):
         arrays.append(arr)
         names.append(oc.name)
     return pa.table(arrays, names=names)
+
+
+def described_to_columns(schema, dense: List[np.ndarray]) -> Dict[str, list]:
+    """to_columns() for dense columns that describe themselves (plan.ColumnDesc; DeviceColumns.group_by): dense[t] holds
+    column t's int64 words.  None for a NULL word, a dictionary's string for a string id, a double for an fp column, a
+    scaled decimal divided by 10 ** scale."""
+    res = {}
+    for d, words in zip(schema, dense):
+        w = np.ascontiguousarray(words).view(np.int64)
+        null = (w == np.int64(d.null_bits)).tolist() if d.nullable else [False] * len(w)
+        if d.is_fp:
+            vals = w.view(np.float64).tolist()
+        elif d.dictionary is not None and d.agg != "count":
+            vals = [None if z else d.dictionary[v] for v, z in zip(w.tolist(), null)]
+        else:
+            vals = w.tolist()
+        col = [None if z else v for v, z in zip(vals, null)]
+        if d.scale and d.agg != "count":
+            col = [None if v is None else v / 10 ** d.scale for v in col]
+        res[d.name] = col
+    return res
+
+
+def described_to_arrow(schema, cols: Dict[str, list]):
+    """{column name: python list} of described_to_columns -> pyarrow.Table with the columns' names and types."""
+    import pyarrow as pa
+    arrays = []
+    for d in schema:
+        v = cols[d.name]
+        if d.dictionary is not None and d.agg != "count":
+            ty = pa.string()
+        elif d.is_fp or (d.scale and d.agg != "count"):
+            ty = pa.float64()
+        elif d.agg in ("count", "sum"):
+            ty = pa.int64()
+        else:
+            ty = {1: pa.int8(), 2: pa.int16(), 4: pa.int32(), 8: pa.int64()}.get(d.type.size, pa.int64())
+        arrays.append(pa.array(v, type=ty))
+    return pa.table(arrays, names=[d.name for d in schema])

@@ -711,6 +711,65 @@ int32_t hdk_hip_filter_columns(const int64_t* cols, uint64_t capacity, int32_t n
                                void* workspace, size_t workspace_bytes, int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GROUP BY over dense result columns on the device: one row per run of adjacent rows with equal keys.
+ * The device form, for a result whose columns sit in HBM, of the reference's per-slot merge of partial results
+ * (reduceOneSlot, omniscidb/QueryEngine/ResultSetReduction.cpp) with the NULL rules of the _skip_val functions
+ * (omniscidb/QueryEngine/RuntimeFunctions.cpp:612-681, 841-867): a second aggregation step over a first step's result
+ * (a roll-up, SELECT DISTINCT, the outer half of COUNT(DISTINCT)).
+ * Input: `num_cols` columns of `num_rows` 8-byte words, column t at cols + t * capacity, NULLs in band -- what
+ * hdk_hip_columnarize_result, hdk_hip_filter_columns and hdk_hip_sort_columns write.  Rows with equal keys must be
+ * ADJACENT: a precondition, which hdk_hip_sort_columns on the key columns establishes.  A RUN is a maximal stretch of
+ * adjacent rows whose words in every one of the `num_keys` (1..HDK_HIP_MAX_GROUP_KEYS) columns key_cols[] are BIT-EQUAL:
+ * NULL equals NULL, -0.0 differs from +0.0, NaNs are compared by pattern -- how the group-by tables compare 8-byte keys,
+ * and the equivalence that the sort's total order makes adjacent.  Unsorted input is not an error: every run becomes a row.
+ * Output: one row per run, in input order; output column j (of `num_outs`, 1..HDK_HIP_MAX_GROUP_OUTS) at
+ * out_cols + j * out_capacity, in the order of `outs`:
+ *   HDK_AGG_ID      the run's word of column `col`, which must be one of key_cols (SELECT DISTINCT k: outs = [ID(k)]; a key
+ *                   need not be projected)
+ *   HDK_AGG_COUNT   col < 0: COUNT(*), the rows of the run; else the words of `col` that are not NULL.  An int64, never NULL
+ *   HDK_AGG_SUM     over the non-NULL words: int64 two's-complement wrapping addition, or (is_fp) a sum of doubles in an
+ *                   unspecified association (the same on every run of the same call)
+ *   HDK_AGG_MIN / HDK_AGG_MAX   over the non-NULL words by < / > on int64 or (is_fp) on doubles
+ * A word is NULL when the out is nullable and the word EQUALS null_bits (a bit compare, the rule of hdk_hip_order_entry);
+ * with nullable == 0 every word is a value.  SUM / MIN / MAX of a run without a non-NULL word give null_bits.  Whether a
+ * run has a value is tracked beside the value, so a sum that happens to equal null_bits is still stored as that sum (and
+ * reads as NULL to whoever reads the column afterwards, as in the reference).  A NaN inside an aggregated double column
+ * leaves that run's SUM / MIN / MAX unspecified.
+ * *row_count (device) ALWAYS receives the true number of runs; rows at or beyond out_capacity are not written, and nothing
+ * outside [0, min(runs, out_capacity)) of an output column is touched.  out_cols == NULL (or out_capacity == 0): count
+ * only.  The input is not modified, and no two of cols, out_cols, row_count and workspace may overlap (out_cols in a
+ * count-only call has no bytes and overlaps nothing).
+ * `workspace`: hdk_hip_group_columns_workspace_bytes(num_rows, num_outs) bytes of device memory, 8-byte aligned (host
+ * arithmetic only: per tile of 4 096 rows 4 bytes and 12 bytes per out, plus at most 1 KiB), or NULL -- the library then
+ * takes it from the stream's memory pool (hipMallocAsync), as its siblings do.
+ * ASYNCHRONOUS on `stream`: four launches (count, scan, carry scan, reduce; two in a count-only call) ordered by the stream
+ * alone; the host never waits (as hdk_hip_filter_columns).  Output and *row_count are complete when `stream` has drained.
+ * Errors, all found before any device is touched (HDK_HIP_ERR_INVALID_ARG with a message): a NULL cols / key_cols / outs /
+ * row_count, num_keys outside 1..8, num_outs outside 1..16, a column index outside [0, num_cols) (col < 0 is COUNT(*) for
+ * HDK_AGG_COUNT only), an ID whose column is not a key, a kind outside the five, num_rows >= 2^32, num_rows > capacity,
+ * overlapping blocks, a workspace that is too small or not 8-byte aligned.
+ * num_rows == 0: *row_count = 0 is stored on the stream, nothing else is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define HDK_HIP_MAX_GROUP_KEYS 8
+#define HDK_HIP_MAX_GROUP_OUTS 16
+
+typedef struct hdk_hip_group_out {
+  int32_t col;        /* input column; ignored for COUNT(*) (col < 0) */
+  uint8_t kind;       /* HDK_AGG_ID: the run's value of a KEY column (col must be in key_cols);
+                         HDK_AGG_COUNT (col < 0: rows of the run; else non-NULL words), HDK_AGG_SUM, HDK_AGG_MIN, HDK_AGG_MAX */
+  uint8_t is_fp;      /* words are doubles (SUM / MIN / MAX as doubles); else int64 */
+  uint8_t nullable;   /* 0: null_bits is an ordinary value */
+  uint8_t pad_;
+  int64_t null_bits;  /* the input column's in-band NULL, as in hdk_hip_order_entry */
+} hdk_hip_group_out;
+
+size_t hdk_hip_group_columns_workspace_bytes(uint64_t num_rows, int32_t num_outs);
+int32_t hdk_hip_group_columns(const int64_t* cols, uint64_t capacity, int32_t num_cols, uint64_t num_rows,
+                              const int32_t* key_cols, int32_t num_keys, const hdk_hip_group_out* outs, int32_t num_outs,
+                              int64_t* out_cols, uint64_t out_capacity, uint64_t* row_count, void* workspace,
+                              size_t workspace_bytes, int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Environment switches (MI355X addition; no reference counterpart: the reference's knobs are Config fields,
  * Shared/Config.h).  libhdk_hip.so reads its HDK_HIP_* variables (tests and A/B measurements, none needed
  * in production) ONCE per process, at the first launch that asks for one -- never per launch, so a host that calls
