@@ -48,6 +48,25 @@ inline bool plain_outer_col(const hdk_hip_plan* p, const hdk_hip_expr& e, int* c
   return true;
 }
 
+// What a specialised kernel must leave out of target `tg`'s aggregate when its argument arrives as `width` bytes of an integer
+// column (8 for a computed value or a double): false = nothing, true = values equal to *skip_val.  As eval_target_arg:
+//   - a nullable argument under a *_skip_val call: the argument's NULL;
+//   - an argument that cannot be NULL under a *_skip_val call (every aggregate of a non-grouped query is one, whatever the
+//     declared nullability: QE/TargetExprBuilder.cpp:546-551): the call still drops a value equal to the SLOT's sentinel
+//     (`val != skip_val`) -- INT64_MIN under SUM(bigint), the type's minimum under COUNT / MIN / MAX, NULL_DOUBLE.  A narrow
+//     column cannot hold a sentinel from outside its type (SUM's NULL_BIGINT over an INT): nothing to skip then.
+inline bool target_skip_value(const hdk_hip_target& tg, int width, bool fp, int64_t* skip_val) {
+  *skip_val = tg.arg.null_val;
+  if (!tg.skip_null) return false;
+  if (tg.arg.nullable) return true;
+  if (!fp && width < 8) {
+    const int64_t lo = -(1ll << (8 * width - 1));
+    if (tg.null_val < lo || tg.null_val > -lo - 1) return false;
+  }
+  *skip_val = tg.null_val;
+  return true;
+}
+
 // INNER, or SEMI: the same probe over a table whose fill let the first row of a key win
 inline bool join_type_inner_like(int32_t type) { return type == HDK_JOIN_INNER || type == HDK_JOIN_SEMI; }
 

@@ -865,11 +865,12 @@ static bool match_fast(const hdk_hip_plan* p, const LaunchShape& shape, FastArgs
     if (col.kind != HDK_COL_INT && !fp) return false;
     if (tg.agg != HDK_AGG_COUNT && (tg.arg_is_fp != 0) != fp) return false;  // no int->fp promotion here
     if (col.width != 4 && col.width != 8) return false;
-    const int nullable = tg.skip_null && tg.arg.nullable;
-    if (vw && fa->val_nullable != nullable) return false;
+    int64_t skip_val;
+    const int nullable = target_skip_value(tg, e.nsteps ? 8 : col.width, fp, &skip_val);
+    if (vw && (fa->val_nullable != nullable || (nullable && fa->val_null != skip_val))) return false;  // one value, two NULL conventions
     vw = col.width;
     fa->val_buf_idx = col.buf_idx;
-    fa->val_null = tg.arg.null_val;
+    fa->val_null = skip_val;
     fa->val_nullable = nullable;
     fa->val_is_fp = fp;
     if (e.nsteps == 1) {
@@ -1045,7 +1046,8 @@ static bool match_cols(const hdk_hip_plan* p, const LaunchShape& shape, ColsArgs
     if (fp ? col.width != 8 : (col.width != 1 && col.width != 2 && col.width != 4 && col.width != 8)) return false;
     if (tg.agg != HDK_AGG_COUNT && (tg.arg_is_fp != 0) != fp) return false;  // (no int -> fp promotion, no float accumulators)
     if (tg.arg_is_fp == HDK_FP_SLOT_FLOAT) return false;
-    const int nullable = tg.skip_null && tg.arg.nullable;
+    int64_t skip_val;
+    const int nullable = target_skip_value(tg, col.width, fp, &skip_val);
     int ci = -1;
     for (int i = 0; i < ca->ncols; ++i) {
       if (ca->col[i].buf_idx == col.buf_idx) ci = i;
@@ -1057,8 +1059,8 @@ static bool match_cols(const hdk_hip_plan* p, const LaunchShape& shape, ColsArgs
       ca->col[ci].width = col.width;
       ca->col[ci].fp = fp;
       ca->col[ci].nullable = nullable;
-      ca->col[ci].null_val = tg.arg.null_val;
-    } else if (ca->col[ci].nullable != nullable || (nullable && ca->col[ci].null_val != tg.arg.null_val) || ca->col[ci].width != col.width ||
+      ca->col[ci].null_val = skip_val;
+    } else if (ca->col[ci].nullable != nullable || (nullable && ca->col[ci].null_val != skip_val) || ca->col[ci].width != col.width ||
                ca->col[ci].fp != static_cast<int32_t>(fp)) {
       return false;
     }

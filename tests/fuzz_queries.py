@@ -132,6 +132,13 @@ def make_tables_wide(rng, n, nd):
     dec = rng.integers(-300, 900, n, dtype=np.int64)
     dec[rng.random(n) < 0.03] = A.NULL_BIGINT
     cols.update({"f32": f32, "ts": ts, "dec": dec})
+    # two columns declared NOT NULL: nn32 holds INT32_MIN -- a value there -- in about 1 % of its rows, nn64 is non-negative.
+    # Their generator is seeded from the columns drawn so far and takes nothing from `rng`: every seed keeps the data and the
+    # queries it had.
+    rng_nn = np.random.default_rng([int(x) & 0xFFFFFFFF for x in cols["v64"][:4]] + [n, nd])
+    nn32 = rng_nn.integers(-500, 500, n).astype(np.int32)
+    nn32[rng_nn.random(n) < 0.01] = A.NULL_INT
+    cols.update({"nn32": nn32, "nn64": rng_nn.integers(0, 10**9, n, dtype=np.int64)})
     # a DATE in days on both sides (bucketized join tables) and a dimension key with NULL rows (IS NOT DISTINCT FROM)
     from hdk_amd.ir import DATE32
     day = (17000 + rng.integers(0, nd // 2 + 20, n)).astype(np.int32)
@@ -147,12 +154,16 @@ def make_tables_wide(rng, n, nd):
     # fragment shapes the base generator never draws: many fragments shorter than a tile, exactly one tile, one row more
     frag = int(rng.choice([frag, frag, n // 61 + 1, 2048, 8193]))
     st.import_numpy("fact", cols, fragment_size=frag,
-                    types={"ts": Type("timestamp", 8, unit="s"), "dec": Type("decimal", 8, scale=2), "day": DATE32})
+                    types={"ts": Type("timestamp", 8, unit="s"), "dec": Type("decimal", 8, scale=2), "day": DATE32,
+                           "nn32": Type("int", 4, False), "nn64": Type("int", 8, False)})
     return st
 
 
-def random_query_wide(rng, projection=False):
-    """random_query, then seeded rewrites towards the rows the base generator never draws."""
+def random_query_wide(rng, projection=False, not_null=True):
+    """random_query, then seeded rewrites towards the rows the base generator never draws.  not_null: with a small
+    probability an aggregate's argument or a filter leaf reads one of the NOT NULL columns -- drawn from a generator seeded
+    by the query itself, so `rng` hands out what it did before (tests/routing_corpus.py pins its queries with not_null=False)."""
+    import zlib
     from dataclasses import replace
     from hdk_amd.ir import And, Cast, ExtractYear, INT32, Not, Or
     q = random_query(rng, projection=projection)
@@ -191,4 +202,19 @@ def random_query_wide(rng, projection=False):
             joins = [JoinSpec("ddim", ColRef("day"), "day", typ, null_safe=typ not in ("semi", "anti"))]
         else:
             joins = [JoinSpec("dim", [ColRef("fk2"), ColRef("k8")], ["a", "g"], "semi" if typ != "anti" else "anti")]  # keyed
-    return replace(q, quals=quals, targets=targets, groupby=groupby, joins=joins, bigint_count=bool(rng.random() < 0.3))
+    q = replace(q, quals=quals, targets=targets, groupby=groupby, joins=joins, bigint_count=bool(rng.random() < 0.3))
+    if not not_null:
+        return q
+    rng_nn = np.random.default_rng(zlib.crc32(repr(q).encode()))
+    for i, t in enumerate(targets):
+        if isinstance(t, Agg) and t.arg is not None and rng_nn.random() < 0.08:
+            targets[i] = Agg(t.kind, ColRef(str(rng_nn.choice(["nn32", "nn64"]))), t.name)
+        elif isinstance(t, Proj) and t.name == "e1" and rng_nn.random() < 0.3:
+            targets[i] = Proj(ColRef("nn32"), "e1")
+    if rng_nn.random() < 0.1:  # (TRUE for the planted INT32_MIN; `= INT32_MIN` finds exactly those rows)
+        leaf = Cmp(ColRef("nn32"), "<", Lit(0)) if rng_nn.random() < 0.7 else Cmp(ColRef("nn32"), "=", Lit(A.NULL_INT))
+        if quals and rng_nn.random() < 0.5:
+            quals = quals[:-1] + [Or(quals[-1], leaf)]
+        else:
+            quals = quals + [leaf]
+    return replace(q, quals=quals, targets=targets)

@@ -192,7 +192,7 @@ def _fuzz_plans():
     out = []
     for i in range(FUZZ_DRAWS):
         wide, proj = i % 4 == 3, i % 5 == 4
-        q = FQ.random_query_wide(rng, projection=proj) if wide else FQ.random_query(rng, projection=proj)
+        q = FQ.random_query_wide(rng, projection=proj, not_null=False) if wide else FQ.random_query(rng, projection=proj)
         try:
             out.append((f"f{i}", compile_query(stw if wide else st, q)))
         except QueryMustRunOnCpu:
