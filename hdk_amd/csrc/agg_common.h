@@ -100,4 +100,36 @@ HDK_DEV int64_t word_combine(int32_t op, int64_t a, int64_t b) {
   }
 }
 
+// one LDS atomic of a value word (the batched interpreter, the join kernels)
+HDK_DEV void vec_lds_op(int32_t wop, int64_t* wp, int64_t v) {
+  switch (wop) {
+    case WOP_ADD_U64: atomicAdd(reinterpret_cast<unsigned long long*>(wp), static_cast<unsigned long long>(v)); break;
+    case WOP_ADD_F64: atomicAdd(reinterpret_cast<double*>(wp), bits_to_double(v)); break;
+    case WOP_MIN_I64: atomicMin(reinterpret_cast<long long*>(wp), static_cast<long long>(v)); break;
+    case WOP_MAX_I64: atomicMax(reinterpret_cast<long long*>(wp), static_cast<long long>(v)); break;
+    case WOP_MIN_F64: {
+      unsigned long long* a = reinterpret_cast<unsigned long long*>(wp);
+      unsigned long long old = *a;
+      const double d = bits_to_double(v);
+      while (d < bits_to_double(static_cast<int64_t>(old))) {
+        const unsigned long long assumed = old;
+        old = atomicCAS(a, assumed, static_cast<unsigned long long>(v));
+        if (old == assumed) break;
+      }
+      break;
+    }
+    default: {
+      unsigned long long* a = reinterpret_cast<unsigned long long*>(wp);
+      unsigned long long old = *a;
+      const double d = bits_to_double(v);
+      while (bits_to_double(static_cast<int64_t>(old)) < d) {
+        const unsigned long long assumed = old;
+        old = atomicCAS(a, assumed, static_cast<unsigned long long>(v));
+        if (old == assumed) break;
+      }
+      break;
+    }
+  }
+}
+
 }  // namespace hdk

@@ -1,5 +1,5 @@
-// host_match.h -- host-side helpers shared by the scan translation units (scan_agg.hip: API + LDS strategies;
-// scan_baseline.hip: open-addressing strategies; scan_project.hip: filter/project), and what they export to each other
+// host_match.h -- host-side helpers shared by the scan translation units (scan_agg.hip: API + LDS strategies; scan_join.hip:
+// their join kernels; scan_baseline.hip: open-addressing strategies; scan_project.hip: filter/project), and what they export to each other
 // (route.h: how a launch is routed to them).
 #pragma once
 #include <string.h>
@@ -207,6 +207,12 @@ int32_t launch_head(const hdk_hip_plan* plan, int8_t* const params[HDK_KP_COUNT]
                     int32_t device_id, void* workspace, hipStream_t s, hdk_hip_plan** d_plan_out, KernParams* kp_out);
 // HIP events around a launch's dominant kernels (HDK_HIP_LAUNCH_RECORD_EVENTS): begin returns the pair to record
 int32_t scan_events_begin(int32_t device_id, hipStream_t s, hipEvent_t* e0, hipEvent_t* e1);
+// for scan_join.hip: strategy, replication and LDS arithmetic of a launch; the resident grid of the interpreter that takes a plan
+// of the LDS strategy; and that interpreter (never the row-at-a-time kernel) armed behind *run_if (nullptr: it always runs)
+LaunchShape base_shape(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props);
+uint32_t interpreter_grid(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, uint32_t lds_bytes, const hdk_hip_device_properties* props);
+int32_t launch_vec_armed(const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, int64_t* slabs, const LaunchShape& shape,
+                         const hdk_hip_kernel_options* ko, hipStream_t s, const uint32_t* run_if);
 
 // ---- scan_fast.hip: the streaming kernel hdk_scan_agg_direct (scan_agg_fast.h), key width kw, value width vw ---------
 struct FastArgs;

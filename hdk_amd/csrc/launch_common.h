@@ -1,4 +1,4 @@
-// launch_common.h -- launch-shape decisions shared by the scan kernels' translation unit.
+// launch_common.h -- launch-shape decisions shared by the scan kernels' translation units (scan_agg.hip, scan_join.hip, ...).
 #pragma once
 #include "agg_common.h"
 #include "host_common.h"

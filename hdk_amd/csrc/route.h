@@ -14,8 +14,8 @@ namespace hdk {
 enum PrePass { PRE_NONE = 0, PRE_CLUSTER_BY_KEY };
 
 // X(enumerator, family, pre-pass and kernels of the launch in order, armed fallbacks included).  The family, not the place in the
-// list, says who launches a route and what surrounds it: LDS* fill slabs that hdk_finalize folds (scan_agg.hip), BH* fold into the
-// output table themselves (scan_bh_packed.hip, scan_bhm.hip, scan_bh.hip; BH_BEHIND: scan_agg.hip), BASELINE: scan_baseline.hip.
+// list, says who launches a route and what surrounds it: LDS* fill slabs that hdk_finalize folds (scan_agg.hip; LDS_JOIN: scan_join.hip),
+// BH* fold into the output table themselves (scan_bh_packed.hip, scan_bhm.hip, scan_bh.hip; BH_BEHIND: scan_join.hip), BASELINE: scan_baseline.hip.
 #define HDK_ROUTE_LIST(X) \
   X(STREAM_DIRECT, LDS, "hdk_scan_agg_direct,hdk_finalize") \
   X(COLS, LDS, "hdk_scan_agg_cols,hdk_finalize") \
@@ -114,7 +114,15 @@ int32_t launch_bh_packed(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip
                          const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, hipStream_t s, bool* launched);
 int32_t launch_bh(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, const hdk_hip_kernel_options* ko,
                   const hdk_hip_device_properties* props, hipStream_t s, bool* launched);
-// scan_agg.hip: a baseline-hash plan with a bounded key behind the sliced join (an internal dense table + hdk_bh_fold_dense)
+// scan_join.hip: the join kernels among the LDS strategy's plans (r->shape.grid: the interpreter's, which stays armed behind them);
+// the clustering pre-pass in front of another route's join probes (fills r->pre_args; *scratch: freed by the caller after the scan)
+bool route_lds_join(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, RouteSet refused,
+                    LaunchRoute* r);
+int32_t launch_lds_join(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp, int64_t* slabs,
+                        const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props, hipStream_t s, bool* launched);
+bool route_cluster_prepass(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, LaunchRoute* r);
+int32_t launch_cluster_prepass(LaunchRoute& r, KernParams* kp, const hdk_hip_device_properties* props, hipStream_t s, void** scratch);
+// ... and a baseline-hash plan with a bounded key behind the sliced join (an internal dense table + hdk_bh_fold_dense)
 bool route_baseline_sliced_join(const hdk_hip_plan* p, const hdk_hip_kernel_options* ko, const hdk_hip_device_properties* props,
                                 RouteSet refused, LaunchRoute* r);
 int32_t launch_baseline_sliced_join(LaunchRoute& r, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,

@@ -26,37 +26,6 @@ struct VecArgs {
   uint32_t bh_pad_;
 };
 
-HDK_DEV void vec_lds_op(int32_t wop, int64_t* wp, int64_t v) {
-  switch (wop) {
-    case WOP_ADD_U64: atomicAdd(reinterpret_cast<unsigned long long*>(wp), static_cast<unsigned long long>(v)); break;
-    case WOP_ADD_F64: atomicAdd(reinterpret_cast<double*>(wp), bits_to_double(v)); break;
-    case WOP_MIN_I64: atomicMin(reinterpret_cast<long long*>(wp), static_cast<long long>(v)); break;
-    case WOP_MAX_I64: atomicMax(reinterpret_cast<long long*>(wp), static_cast<long long>(v)); break;
-    case WOP_MIN_F64: {
-      unsigned long long* a = reinterpret_cast<unsigned long long*>(wp);
-      unsigned long long old = *a;
-      const double d = bits_to_double(v);
-      while (d < bits_to_double(static_cast<int64_t>(old))) {
-        const unsigned long long assumed = old;
-        old = atomicCAS(a, assumed, static_cast<unsigned long long>(v));
-        if (old == assumed) break;
-      }
-      break;
-    }
-    default: {
-      unsigned long long* a = reinterpret_cast<unsigned long long*>(wp);
-      unsigned long long old = *a;
-      const double d = bits_to_double(v);
-      while (bits_to_double(static_cast<int64_t>(old)) < d) {
-        const unsigned long long assumed = old;
-        old = atomicCAS(a, assumed, static_cast<unsigned long long>(v));
-        if (old == assumed) break;
-      }
-      break;
-    }
-  }
-}
-
 template <bool J, bool KEYED = false, bool MANY = false, bool BH = false>
 HDK_DEV void scan_agg_vec_body(const VecArgs& a) {
   extern __shared__ __attribute__((aligned(16))) int64_t lds[];

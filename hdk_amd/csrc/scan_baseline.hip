@@ -1,7 +1,7 @@
 // scan_baseline.hip -- open-addressing group-by strategies: the radix-partitioned passes (scan_agg_partitioned.h), the
 // specialised global-atomics kernel (scan_agg_baseline_fast.h) and the general one (scan_agg_global.h), with their
-// matchers.  A translation unit of its own (scan_agg.hip holds the API and the LDS strategies): the kernels of one
-// strategy family are compiled together and nothing else.
+// matchers.  A translation unit of its own (scan_agg.hip holds the API and the LDS strategies, scan_join.hip their join
+// kernels): the kernels of one strategy family are compiled together and nothing else.
 #include <algorithm>
 #include <vector>
 #define HDK_SCAN_AGG_GLOBAL_KERNEL

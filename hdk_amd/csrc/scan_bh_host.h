@@ -7,7 +7,7 @@ namespace hdk {
 
 struct BhGeom;  // scan_bh_decl.h
 
-// the open-addressing interpreter ARMED behind another strategy's passes: runs only when *run_if == 1 (scan_agg.hip: the sliced
+// the open-addressing interpreter ARMED behind another strategy's passes: runs only when *run_if == 1 (scan_join.hip: the sliced
 // join of a baseline-hash plan); folds into GROUPBY_BUF[0] itself.  `g`: the geometry its route was matched with (route.h)
 int32_t launch_bh_vec_armed(const BhGeom& g, const hdk_hip_plan* plan, const hdk_hip_plan* d_plan, const KernParams& kp,
                             const hdk_hip_device_properties* props, hipStream_t s, const uint32_t* run_if);

@@ -13,7 +13,6 @@
 // a slice of the table that L2 holds, instead of costing one 128-byte memory line each (profiles/r02_c3_pmc.json).
 #pragma once
 #include "agg_common.h"
-#include "scan_agg_vec.h"   // vec_lds_op
 #include "scan_cluster.h"
 #include "watch.h"
 

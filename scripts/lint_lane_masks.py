@@ -30,7 +30,7 @@ def main():
     else:
         text = ""
         with tempfile.TemporaryDirectory() as tmp:
-            for src in ("scan_agg.hip", "scan_baseline.hip", "scan_project.hip", "reduce.hip", "join_build.hip", "init_groups.hip"):
+            for src in ("scan_agg.hip", "scan_join.hip", "scan_baseline.hip", "scan_project.hip", "reduce.hip", "join_build.hip", "init_groups.hip"):
                 out = os.path.join(tmp, src + ".s")
                 subprocess.check_call(["hipcc", "-std=c++17", "-O3", "--offload-arch=gfx950", "-munsafe-fp-atomics",
                                        "-ffp-contract=off", "--cuda-device-only", "-S", src, "-o", out],
