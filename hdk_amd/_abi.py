@@ -19,6 +19,8 @@ MAX_ORDER_ENTRIES = 8
 MAX_HAVING_LEAVES = 8
 MAX_GROUP_KEYS = 8
 MAX_GROUP_OUTS = 16
+MAX_WINDOW_KEYS = 8
+MAX_WINDOW_OUTS = 8
 SORT_NO_SELECT = 1  # hdk_hip_sort_columns flags
 F_AND, F_OR, F_NOT = 64, 65, 66
 PLAN_ABI = 4
@@ -63,6 +65,10 @@ JOIN_INNER, JOIN_LEFT, JOIN_SEMI, JOIN_ANTI = 0, 1, 2, 3
 JOIN_NULL_NONE, JOIN_NULL_NULLABLE, JOIN_NULL_BITWISE = 0, 1, 2
 Q_NON_GROUPED, Q_PERFECT_HASH, Q_BASELINE_HASH, Q_PROJECTION = 0, 1, 2, 3
 AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG, AGG_ID, AGG_SINGLE_VALUE = 0, 1, 2, 3, 4, 5, 6
+# hdk_hip_window_kind (the order of the reference's WindowFunctionKind) and hdk_hip_window_frame
+(WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_PERCENT_RANK, WIN_CUME_DIST, WIN_NTILE, WIN_LAG, WIN_LEAD, WIN_FIRST_VALUE,
+ WIN_LAST_VALUE, WIN_AVG, WIN_MIN, WIN_MAX, WIN_SUM, WIN_COUNT) = range(15)
+FRAME_ROWS, FRAME_RANGE, FRAME_PARTITION = 0, 1, 2
 JC_SMALL_DATE, JC_SIGNED, JC_UNSIGNED, JC_DOUBLE = 0, 1, 2, 3
 (KP_COL_BUFFERS, KP_NUM_FRAGMENTS, KP_LITERALS, KP_NUM_ROWS, KP_FRAG_ROW_OFFSETS, KP_MAX_MATCHED,
  KP_TOTAL_MATCHED, KP_INIT_AGG_VALS, KP_GROUPBY_BUF, KP_ERROR_CODE, KP_NUM_TABLES,
@@ -172,6 +178,14 @@ class GroupOut(C.Structure):
     the word equals null_bits."""
     _fields_ = [("col", C.c_int32), ("kind", C.c_uint8), ("is_fp", C.c_uint8), ("nullable", C.c_uint8), ("pad_", C.c_uint8),
                 ("null_bits", C.c_int64)]
+
+
+class WindowOut(C.Structure):
+    """hdk_hip_window_out: one output of hdk_hip_window_columns: a ranking kind, LAG / LEAD (param = k), NTILE (param = n),
+    FIRST_VALUE / LAST_VALUE or an aggregate of column `col` over the frame, whose word is NULL when the out is nullable and
+    the word equals null_bits."""
+    _fields_ = [("col", C.c_int32), ("kind", C.c_uint8), ("frame", C.c_uint8), ("is_fp", C.c_uint8), ("nullable", C.c_uint8),
+                ("null_bits", C.c_int64), ("param", C.c_int64)]
 
 
 class KernelOptions(C.Structure):

@@ -473,5 +473,6 @@ size_t hdk_hip_sizeof_join(void) { return sizeof(hdk_hip_join); }
 size_t hdk_hip_sizeof_device_properties(void) { return sizeof(hdk_hip_device_properties); }
 size_t hdk_hip_sizeof_kernel_options(void) { return sizeof(hdk_hip_kernel_options); }
 size_t hdk_hip_sizeof_group_out(void) { return sizeof(hdk_hip_group_out); }
+size_t hdk_hip_sizeof_window_out(void) { return sizeof(hdk_hip_window_out); }
 
 }  // extern "C"

@@ -25,7 +25,8 @@ from .hip_mgr import DeviceBuffer, HipMgr
 from .ir import QueryMustRunOnCpu, QueryUnit
 from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, GROUP_KINDS, ColumnDesc, CompiledPlan, Having, columnar_init_vals,
                    compact_init_vals, compile_query, describe_columns, eff_key_count, has_count_distinct, regroup_columns,
-                   resolve_having, resolve_having_columns, resolve_order_by, split_count_distinct)
+                   group_windows, resolve_having, resolve_having_columns, resolve_order_by, resolve_window_columns,
+                   split_count_distinct)
 from .storage import ArrowStorage
 
 
@@ -324,6 +325,72 @@ class DeviceColumns:
             if src is not self:
                 src.free()
         return out
+
+    def window(self, partition_by, order_by, outs, presorted: bool = False) -> "DeviceColumns":
+        """Window functions OVER (PARTITION BY `partition_by` ORDER BY `order_by`) on the device (hdk_hip_window_columns;
+        the reference's WindowFunctionContext, QE/WindowContext.cpp) -> a new DeviceColumns that carries a schema: these
+        columns followed by one column per out, every input row once; this object stays valid.  `partition_by`: columns
+        by index, name or ir.TargetRef; `order_by`: ir.OrderEntry items; `outs`: ir.Window items, of which kind, arg,
+        frame, param and name are read (plan.resolve_window_columns has the rules for type and nullability).  The library
+        reads ADJACENT rows: unless `presorted` says that the rows already are in that order, they are ordered by the
+        partition keys ascending with NULLs last, then by `order_by` (hdk_hip_sort_columns, stable), straight into the
+        first columns of the one block that also holds the window columns, which the library writes.  More outs than one
+        call takes go through further calls over the same sorted columns."""
+        part_cols, order, spec, descs = resolve_window_columns(self.columns(), partition_by, order_by, outs)
+        nc, nw, n = self.num_cols, len(spec), self.num_rows
+        out = DeviceColumns(self.compiled, self.mgr, self.device_id, None, 0, 0, self.error_code, self.columns() + descs)
+        if n == 0:
+            return out
+        if self.block is None or not self.block.ptr:
+            raise ValueError("the columns have been freed")
+        entries = [] if presorted else [(k, False, False) for k in part_cols] + order
+        if len(entries) > A.MAX_ORDER_ENTRIES:
+            raise QueryMustRunOnCpu("more than %d partition keys and order entries to sort by" % A.MAX_ORDER_ENTRIES)
+        block = self.mgr.alloc((nc + nw) * n * 8, self.device_id)
+        try:
+            if not entries:
+                for t in range(nc):
+                    self.mgr.copyDeviceToDevice(block.ptr + t * n * 8, self.device_ptr(t), n * 8, self.device_id, self.device_id)
+            else:
+                arr = (A.OrderEntry * len(entries))()
+                for i, (t, desc, nulls_first) in enumerate(entries):
+                    is_fp, nullable, null_bits = self._column_null(t)
+                    arr[i] = A.OrderEntry(t, int(desc), int(nulls_first), int(is_fp), int(nullable), A.to_i64(null_bits))
+                check(lib().hdk_hip_sort_columns(self.block.ptr, self.capacity, nc, n, arr, len(entries), 0, 0, 0, block.ptr, n,
+                                                 None, None, 0, self.device_id, None))
+            pc = (C.c_int32 * max(len(part_cols), 1))(*part_cols)
+            oc = (C.c_int32 * max(len(order), 1))(*[t for t, _, _ in order])
+            for j0 in range(0, nw, A.MAX_WINDOW_OUTS):
+                part = spec[j0:j0 + A.MAX_WINDOW_OUTS]
+                warr = (A.WindowOut * len(part))()
+                for j, w in enumerate(part):
+                    is_fp, nullable, null_bits = self._column_null(w.col) if w.col >= 0 else (False, False, 0)
+                    warr[j] = A.WindowOut(w.col, w.kind, w.frame, int(is_fp), int(nullable), A.to_i64(null_bits), w.param)
+                check(lib().hdk_hip_window_columns(block.ptr, n, nc, n, pc, len(part_cols), oc, len(order), warr, len(part),
+                                                   block.ptr + (nc + j0) * n * 8, n, None, 0, self.device_id, None))
+            self.mgr.synchronizeStream(self.device_id)
+        except Exception:
+            block.free()
+            raise
+        out.block, out.capacity, out.num_rows = block, n, n
+        return out
+
+    def windows(self, windows) -> "DeviceColumns":
+        """A unit's window functions (QueryUnit.windows): one window() per distinct (partition_by, order_by) in order of
+        first appearance, each over the result of the one before, whose block is handed back.  A window without a name is
+        called <kind>_<number of columns + its index in `windows`>.  -> a new DeviceColumns; this object stays valid."""
+        windows = [dataclasses.replace(w, name=w.name or f"{w.kind}_{self.num_cols + i}") for i, w in enumerate(windows)]
+        if not windows:
+            return self.sort([])  # nothing to add: every row, copied
+        cols = self
+        for partition_by, order_by, idx in group_windows(windows):
+            try:
+                nxt = cols.window(partition_by, order_by, [windows[i] for i in idx])
+            finally:
+                if cols is not self:
+                    cols.free()
+            cols = nxt
+        return cols
 
     def free(self):
         if self.block is not None:
@@ -799,6 +866,8 @@ class Executor:
         if result not in ("buffer", "columns"):
             raise ValueError(f"result must be 'buffer' or 'columns', not {result!r}")
         sq = q.query if isinstance(q, CompiledPlan) else q
+        if sq.windows and result == "buffer":
+            raise ValueError("windows need result='columns': they read the dense result columns, not a hash-table buffer")
         if has_count_distinct(sq):
             if result == "buffer":
                 raise ValueError("count_distinct needs result='columns': it regroups the dense result columns of an inner "
@@ -827,10 +896,16 @@ class Executor:
                         finally:
                             cols.free()
                         cols = kept
+                    if sq.windows:  # after HAVING and before the SortInfo, which may name a window column
+                        try:
+                            windowed = cols.windows(sq.windows)
+                        finally:
+                            cols.free()
+                        cols = windowed
                     if not sorts:
                         return cols
                     try:
-                        return cols.sort(step.cp.order_by, sq.limit, sq.offset)
+                        return cols.sort(sq.order_by if sq.windows else step.cp.order_by, sq.limit, sq.offset)
                     finally:
                         cols.free()
                 return step.run()
@@ -859,6 +934,12 @@ class Executor:
             finally:
                 out.free()
             out = kept
+        if rg.windows:
+            try:
+                windowed = out.windows(rg.windows)
+            finally:
+                out.free()
+            out = windowed
         if not (rg.order_by or rg.limit is not None or rg.offset):
             return out
         try:

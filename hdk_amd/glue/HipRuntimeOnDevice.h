@@ -246,4 +246,24 @@ inline void group_columns_on_device(const int64_t* cols, const size_t capacity, 
                               device_id, nullptr));
 }
 
+// The window step for a result whose dense columns are on the device and sorted by (partition keys, order entries)
+// (sort_columns_on_device): WindowFunctionContext's per-partition computation (QueryEngine/WindowContext.cpp) over the
+// previous step's materialised result.  One word per input row and out, in input row order, column j of `outs` at
+// out_cols + j * out_capacity (out_capacity >= num_rows); partitions and peer groups are stretches of adjacent rows whose
+// words in `part_cols` (and `order_cols`) are bit-equal.  `workspace` comes from the BufferProvider
+// (window_columns_workspace_bytes(num_rows, num_outs) bytes) or is null (the stream's memory pool).  Asynchronous on the
+// device's stream: the host never waits.
+inline size_t window_columns_workspace_bytes(const size_t num_rows, const int num_outs) {
+  return hdk_hip_window_columns_workspace_bytes(static_cast<uint64_t>(num_rows), num_outs);
+}
+inline void window_columns_on_device(const int64_t* cols, const size_t capacity, const int num_cols, const size_t num_rows,
+                                     const int32_t* part_cols, const int num_part, const int32_t* order_cols, const int num_order,
+                                     const hdk_hip_window_out* outs, const int num_outs, int64_t* out_cols,
+                                     const size_t out_capacity, int8_t* workspace, const size_t workspace_bytes,
+                                     const int device_id) {
+  check(hdk_hip_window_columns(cols, static_cast<uint64_t>(capacity), num_cols, static_cast<uint64_t>(num_rows), part_cols, num_part,
+                               order_cols, num_order, outs, num_outs, out_cols, static_cast<uint64_t>(out_capacity), workspace,
+                               workspace_bytes, device_id, nullptr));
+}
+
 }  // namespace hip_rt

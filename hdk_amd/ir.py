@@ -234,6 +234,28 @@ class OrderEntry:
     nulls_first: bool = False
 
 
+WINDOW_KINDS = ("row_number", "rank", "dense_rank", "percent_rank", "cume_dist", "ntile", "lag", "lead", "first_value",
+                "last_value", "avg", "min", "max", "sum", "count")  # hdk::ir::WindowFunctionKind, IR/OpTypeEnums.h:95-112
+WINDOW_FRAMES = ("rows", "range", "partition")
+
+
+@dataclass(frozen=True)
+class Window:
+    """One window function over the unit's result columns (hdk::ir::WindowFunction): kind in WINDOW_KINDS OVER (PARTITION
+    BY partition_by ORDER BY order_by).  `arg` and the partition keys name OUTPUT columns: a TargetRef, a target index or
+    an output name (arg None: COUNT(*), and the ranking kinds take none).  `frame`: every frame starts at the partition's
+    first row and ends at the row itself ("rows"), at its last peer ("range") or at the partition's last row
+    ("partition"); None takes the reference's default -- "partition" without order entries, else "range" for count / sum /
+    avg and "rows" for min / max / last_value.  `param`: NTILE's n, LAG / LEAD's k (default 1), a constant."""
+    kind: str
+    arg: Optional[Union[Expr, int, str]] = None
+    partition_by: Sequence = ()
+    order_by: Sequence["OrderEntry"] = ()
+    frame: Optional[str] = None
+    param: Optional[Union[int, Expr]] = None
+    name: Optional[str] = None
+
+
 @dataclass
 class QueryUnit:
     """What one execution step needs (cf. RelAlgExecutionUnit)."""
@@ -256,3 +278,6 @@ class QueryUnit:
     # Cmp(TargetRef, op, TargetRef) (a literal on the left is swapped, the operator mirrored); applied to the dense result
     # columns on the device before order_by / limit / offset (result="columns")
     having: List[Cond] = field(default_factory=list)
+    # window functions over the result columns, applied on the device after HAVING and before order_by / limit / offset
+    # (result="columns"): each adds a column after the targets, in this order; order_by may name one
+    windows: List[Window] = field(default_factory=list)

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _abi as A
 from .ir import (Agg, And, BinOp, Cast, Cmp, ColRef, Expr, ExtractYear, KeyRef, Lit, Not, Or, QueryMustRunOnCpu,
-                 QueryUnit, TargetRef, Type)
+                 QueryUnit, TargetRef, Type, Window, WINDOW_FRAMES, WINDOW_KINDS)
 from .storage import ArrowStorage, Table
 
 BASELINE_THRESHOLD = 1_000_000  # Config.exec.group_by.baseline_threshold (Shared/Config.h:51)
@@ -413,6 +413,139 @@ def regroup_columns(cols: List[ColumnDesc], keys, outs) -> Tuple[List[int], List
         spec.append((kind, t))
         descs.append(d)
     return key_cols, spec, descs
+
+
+WINDOW_RANKING = ("row_number", "rank", "dense_rank", "percent_rank", "cume_dist", "ntile")
+WINDOW_AGGREGATES = ("avg", "min", "max", "sum", "count")
+
+
+@dataclass(frozen=True)
+class WindowSpec:
+    """One resolved window out: the fields of hdk_hip_window_out but the column's NULL (kind and frame as the enums'
+    values, col -1 for COUNT(*) and the ranking kinds)."""
+    kind: int
+    col: int
+    frame: int
+    param: int
+
+
+def default_window_frame(kind: str, ordered: bool) -> str:
+    """The reference's frame for a window function without an explicit one: the whole partition without order entries;
+    with them, up to the last peer for count / sum / avg (window_function_requires_peer_handling,
+    QE/WindowContext.cpp:425-441) and up to the row for the rest (its running MIN / MAX and LAST_VALUE)."""
+    if not ordered:
+        return "partition"
+    return "range" if kind in ("count", "sum", "avg") else "rows"
+
+
+def resolve_window_columns(cols: List[ColumnDesc], partition_by, order_by, outs):
+    """DeviceColumns.window's arguments resolved against the columns `cols`: -> (partition column indices, the order
+    entries as (column, desc, nulls_first), one WindowSpec per out, the ColumnDesc of every NEW column: column
+    len(cols) + j for out j).  `partition_by`: columns by index, name or TargetRef; `order_by`: ir.OrderEntry items;
+    `outs`: ir.Window items, whose own partition_by / order_by are not read.  Ranking kinds and counts are int64 and never
+    NULL, PERCENT_RANK / CUME_DIST doubles that are never NULL, AVG a nullable double; LAG / LEAD have the argument's type
+    and are nullable, FIRST_VALUE / LAST_VALUE keep its type and nullability, SUM / MIN / MAX have its type and are
+    nullable.  A ValueError: an unknown column, kind or frame, a missing or superfluous argument, SUM / AVG of a
+    dictionary-encoded column.  What the library cannot express must run on the CPU: an argument or key that is not an
+    output column, more than 8 partition or order keys, an order entry on a dictionary-encoded column, a LAG / LEAD /
+    NTILE parameter that is not a constant."""
+    by_name = {c.name: i for i, c in enumerate(cols)}
+
+    def column(t, what):
+        if isinstance(t, TargetRef):
+            t = t.target
+        if isinstance(t, Expr):
+            raise QueryMustRunOnCpu(f"window {what} {t!r} is not an output column")
+        if isinstance(t, str):
+            if t not in by_name:
+                raise ValueError(f"window {what} names no column: {t!r}")
+            return by_name[t]
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < len(cols):
+            raise ValueError(f"window {what} column index {t!r} outside 0..{len(cols) - 1}")
+        return int(t)
+
+    part_cols = [column(k, "partition key") for k in partition_by]
+    if len(part_cols) > A.MAX_WINDOW_KEYS or len(order_by) > A.MAX_WINDOW_KEYS:
+        raise QueryMustRunOnCpu("more than %d window partition keys or order entries" % A.MAX_WINDOW_KEYS)
+    order = [(column(e.target, "order entry"), bool(e.desc), bool(e.nulls_first)) for e in order_by]
+    for t, _, _ in order:  # (a partition key only has to make equal ids adjacent)
+        if cols[t].dictionary is not None:
+            raise QueryMustRunOnCpu(f"window ORDER BY a dictionary-encoded column ({cols[t].name}): id order is not string order")
+    outs = list(outs)
+    if not outs:
+        raise ValueError("a window step needs at least one out")
+    int64 = Type("int", 8, False)
+    spec, descs = [], []
+    for j, w in enumerate(outs):
+        at = len(cols) + j
+        if not isinstance(w, Window) or w.kind not in WINDOW_KINDS:
+            raise ValueError(f"window out {j}: {w!r} is no ir.Window of a kind in {WINDOW_KINDS}")
+        frame = w.frame if w.frame is not None else default_window_frame(w.kind, bool(order))
+        if frame not in WINDOW_FRAMES:
+            raise ValueError(f"window frame {frame!r} (rows, range or partition)")
+        param = w.param.value if isinstance(w.param, Lit) else w.param
+        if param is None:
+            param = 1 if w.kind in ("lag", "lead") else 0
+        if isinstance(param, bool) or not isinstance(param, (int, np.integer)):
+            raise QueryMustRunOnCpu(f"window {w.kind} with the parameter {w.param!r}: it must be an integer constant")
+        if param < 0 or (w.kind == "ntile" and param < 1):
+            raise ValueError(f"window {w.kind} with the parameter {param}")
+        name = w.name or f"{w.kind}_{at}"
+        kind, frame_code = WINDOW_KINDS.index(w.kind), WINDOW_FRAMES.index(frame)
+        if w.kind in WINDOW_RANKING:
+            if w.arg is not None:
+                raise ValueError(f"{w.kind} takes no argument")
+            fp = w.kind in ("percent_rank", "cume_dist")
+            descs.append(ColumnDesc(name, fp, False, 0, Type("fp", 8, False) if fp else int64, at, "agg", w.kind))
+            spec.append(WindowSpec(kind, -1, frame_code, int(param)))
+            continue
+        if w.arg is None:
+            if w.kind != "count":
+                raise ValueError(f"{w.kind} needs a column")
+            descs.append(ColumnDesc(name, False, False, 0, int64, at, "agg", "count"))
+            spec.append(WindowSpec(kind, -1, frame_code, 0))
+            continue
+        t = column(w.arg, "argument")
+        src = cols[t]
+        null_bits = src.null_bits if src.nullable else A.to_i64(A.NULL_DOUBLE_BITS) if src.is_fp else A.NULL_BIGINT
+        if w.kind == "count":
+            d = ColumnDesc(name, False, False, 0, int64, at, "agg", "count")
+        elif w.kind in ("sum", "avg"):
+            if src.dictionary is not None or src.type.kind == "dict":
+                raise ValueError(f"{w.kind.upper()} of a dictionary-encoded column ({src.name}): string ids do not add up")
+            if w.kind == "avg":
+                d = ColumnDesc(name, True, True, A.to_i64(A.NULL_DOUBLE_BITS), Type("fp", 8, True), at, "agg", "avg", None, src.scale)
+            else:
+                ty = src.type if src.is_fp else Type(src.type.kind if src.type.kind == "decimal" else "int", 8, True,
+                                                     src.type.scale)
+                d = ColumnDesc(name, src.is_fp, True, null_bits, ty, at, "agg", "sum", None, src.scale)
+        elif w.kind in ("first_value", "last_value"):
+            d = ColumnDesc(name, src.is_fp, src.nullable, src.null_bits, src.type, at, "agg", w.kind, src.dictionary, src.scale)
+        else:  # lag, lead, min, max: the argument's type, NULL where there is no row or no value
+            d = ColumnDesc(name, src.is_fp, True, null_bits, src.type, at, "agg", w.kind, src.dictionary, src.scale)
+        descs.append(d)
+        spec.append(WindowSpec(kind, t, frame_code, int(param)))
+    names = [c.name for c in cols] + [d.name for d in descs]
+    if len(set(names)) != len(names):
+        raise ValueError(f"a window column's name is taken: {names}")
+    return part_cols, order, spec, descs
+
+
+def group_windows(windows) -> List[Tuple[tuple, tuple, List[int]]]:
+    """A unit's windows by distinct (partition_by, order_by) specification in order of first appearance: -> [(partition_by,
+    order_by, indices into `windows`)].  One DeviceColumns.window call serves each."""
+    groups: List[Tuple[tuple, tuple, List[int]]] = []
+    for i, w in enumerate(windows):
+        if not isinstance(w, Window):
+            raise ValueError(f"windows[{i}] is no ir.Window: {w!r}")
+        key = (tuple(w.partition_by), tuple(w.order_by))
+        for g in groups:
+            if (g[0], g[1]) == key:
+                g[2].append(i)
+                break
+        else:
+            groups.append((key[0], key[1], [i]))
+    return groups
 
 
 @dataclass
@@ -1302,7 +1435,10 @@ def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
     if _has_sort_info(q):
         if kind == A.Q_NON_GROUPED:
             raise QueryMustRunOnCpu("ORDER BY / LIMIT / OFFSET on a non-grouped query: it has no dense device columns")
-        order_by = resolve_order_by(out_cols, int(p.num_targets), q.order_by)
+        if not q.windows:  # (with windows the entries may name a window column: DeviceColumns.sort resolves them)
+            order_by = resolve_order_by(out_cols, int(p.num_targets), q.order_by)
+    if q.windows and kind == A.Q_NON_GROUPED:
+        raise QueryMustRunOnCpu("window functions on a non-grouped query: it has no dense device columns")
     cp = CompiledPlan(plan=p, query=q, init_vals=np.array(init_vals, dtype=np.int64),
                       slot_widths=slot_widths, input_cols=list(b.cols),
                       inner_tables=[t.name for t in b.inner], join_infos=join_infos,
@@ -1416,6 +1552,7 @@ class Regroup:
     order_by: list
     limit: Optional[int]
     offset: int
+    windows: list = field(default_factory=list)
 
 
 def has_count_distinct(q: QueryUnit) -> bool:
@@ -1461,5 +1598,5 @@ def split_count_distinct(q: QueryUnit) -> Tuple[QueryUnit, Regroup]:
         else:
             raise ValueError(f"unknown aggregate {t.kind!r}")
     inner = dataclasses.replace(q, groupby=list(q.groupby) + [arg], targets=inner_targets, order_by=[], limit=None, offset=0,
-                                having=[])
-    return inner, Regroup(list(range(nk)), outs, list(q.having), list(q.order_by), q.limit, q.offset)
+                                having=[], windows=[])
+    return inner, Regroup(list(range(nk)), outs, list(q.having), list(q.order_by), q.limit, q.offset, list(q.windows))

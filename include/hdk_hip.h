@@ -770,6 +770,92 @@ int32_t hdk_hip_group_columns(const int64_t* cols, uint64_t capacity, int32_t nu
                               size_t workspace_bytes, int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Window functions over dense result columns on the device: one word per input row and output.
+ * The device form, for a result whose columns sit in HBM, of the reference's window step over the previous step's
+ * materialised result (WindowFunctionContext, omniscidb/QueryEngine/WindowContext.cpp and WindowFunctionIR.cpp; the kinds
+ * are hdk::ir::WindowFunctionKind, omniscidb/IR/OpTypeEnums.h:95-112, in the same order).
+ * Input: `num_cols` columns of `num_rows` 8-byte words, column t at cols + t * capacity, NULLs in band -- what
+ * hdk_hip_columnarize_result, hdk_hip_filter_columns, hdk_hip_sort_columns and hdk_hip_group_columns write.
+ * A PARTITION is a maximal stretch of adjacent rows whose words in every one of the `num_part` (0..HDK_HIP_MAX_WINDOW_KEYS)
+ * columns part_cols[] are BIT-EQUAL (the equivalence of hdk_hip_group_columns: NULL equals NULL); num_part == 0 makes the
+ * whole input one partition.  A PEER GROUP is a maximal stretch inside a partition whose words in every one of the
+ * `num_order` (0..HDK_HIP_MAX_WINDOW_KEYS) columns order_cols[] are bit-equal too; num_order == 0 makes every row of a
+ * partition a peer.  Adjacency is a PRECONDITION, which hdk_hip_sort_columns on (partition keys, order entries)
+ * establishes; unsorted input is not an error: every stretch becomes a partition.  Order keys are read for equality
+ * only: direction and NULL placement belong to the sort.
+ * Deviation from the reference: bit equality differs from the reference's comparator for -0.0 / +0.0 (two peer groups
+ * here) and for NaNs (compared by pattern) -- the deviation that the sort's total order already makes.
+ * Output: exactly `num_rows` rows in input row order, output j (of `num_outs`, 1..HDK_HIP_MAX_WINDOW_OUTS) at
+ * out_cols + j * out_capacity; only the window columns are written.  out_capacity >= num_rows; nothing at or beyond
+ * num_rows is touched, the input is not modified, and no two of cols, out_cols and workspace may overlap.
+ * For a row r (0-based input row index): start / end are the first and last row of its partition, pstart / pend of its
+ * peer group, size = end - start + 1.  The word written for row r:
+ *   HDK_WIN_ROW_NUMBER    r - start + 1
+ *   HDK_WIN_RANK          pstart - start + 1                                   (index_to_rank, WindowContext.cpp:124-137)
+ *   HDK_WIN_DENSE_RANK    the peer groups of the partition up to and including r's                        (:140-153)
+ *   HDK_WIN_PERCENT_RANK  a double: size == 1 ? 0 : (rank - 1) / (size - 1)                               (:156-170)
+ *   HDK_WIN_CUME_DIST     a double: (pend - start + 1) / size                                             (:173-191)
+ *   HDK_WIN_NTILE         param = n >= 1; the reference's rule, not the SQL standard's:
+ *                         (r - start) / ceil(size / n) + 1                                                (:194-206)
+ *   HDK_WIN_LAG / LEAD    param = k >= 0: the word of `col` at row r - k / r + k when that row is inside [start, end],
+ *                         else null_bits (apply_lag_to_partition, :266-285).  The word is copied unexamined
+ *   HDK_WIN_FIRST_VALUE   the word of `col` at start
+ *   HDK_WIN_LAST_VALUE    the word of `col` at the frame's last row
+ *   HDK_WIN_COUNT / SUM / MIN / MAX / AVG   over the frame of r with the NULL rules of hdk_hip_group_columns: COUNT with
+ *                         col < 0 is COUNT(*), COUNT is never NULL; a word is NULL when the out is nullable and the word
+ *                         EQUALS null_bits; SUM / MIN / MAX give null_bits while the frame has no non-NULL word (whether it
+ *                         has one travels beside the value: a sum equal to the sentinel stays a sum); an int64 SUM wraps; a
+ *                         SUM of doubles has an unspecified association, the same on every run of the same call; AVG is
+ *                         always a double, (double)sum / (double)count as the reference's pair_to_double, and
+ *                         HDK_NULL_DOUBLE_BITS while the count is 0
+ * `frame` is read by the aggregates and by LAST_VALUE only.  Every frame starts at `start`; its last row is
+ *   HDK_FRAME_ROWS        r       (the reference's running MIN / MAX and its LAST_VALUE)
+ *   HDK_FRAME_RANGE       pend    (all peers receive the same word, bit for bit: the reference's peer handling for SUM /
+ *                                  COUNT / AVG, window_function_requires_peer_handling, WindowContext.cpp:425-441)
+ *   HDK_FRAME_PARTITION   end     (every row of the partition receives the same word: the reference without order keys)
+ * With num_order == 0, RANGE and PARTITION coincide.  `col` is ignored for the six ranking kinds.
+ * `workspace`: hdk_hip_window_columns_workspace_bytes(num_rows, num_outs) bytes of device memory, 8-byte aligned (host
+ * arithmetic only: 12 bytes per row -- the directory: the last row of every partition and peer group and the ordinal of
+ * every partition's last peer group --, per tile of 4 096 rows 8 bytes and 12 bytes per out, plus at most 2 KiB), or NULL --
+ * the library then takes it from the stream's memory pool (hipMallocAsync), as its siblings do.
+ * ASYNCHRONOUS on `stream`: up to seven launches (count, two scans, carry scan, directory, rows, and a broadcast when an
+ * aggregate has a RANGE or PARTITION frame) ordered by the stream alone; the host never waits.  The output is complete
+ * when `stream` has drained.
+ * Errors, all found before any device is touched (HDK_HIP_ERR_INVALID_ARG with a message): a NULL cols / outs / out_cols,
+ * a NULL part_cols with num_part > 0 or order_cols with num_order > 0, num_part or num_order outside 0..8, num_outs outside
+ * 1..8, num_cols < 1, a column index outside [0, num_cols) (col < 0 is COUNT(*) for HDK_WIN_COUNT only), a kind or frame
+ * outside the enums, param < 0 or an NTILE param < 1, num_rows >= 2^32, num_rows > capacity, out_capacity < num_rows,
+ * overlapping blocks, a workspace that is too small or not 8-byte aligned.
+ * num_rows == 0: HDK_HIP_OK, nothing is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define HDK_HIP_MAX_WINDOW_KEYS 8
+#define HDK_HIP_MAX_WINDOW_OUTS 8
+
+typedef enum hdk_hip_window_kind {
+  HDK_WIN_ROW_NUMBER = 0, HDK_WIN_RANK = 1, HDK_WIN_DENSE_RANK = 2, HDK_WIN_PERCENT_RANK = 3, HDK_WIN_CUME_DIST = 4,
+  HDK_WIN_NTILE = 5, HDK_WIN_LAG = 6, HDK_WIN_LEAD = 7, HDK_WIN_FIRST_VALUE = 8, HDK_WIN_LAST_VALUE = 9, HDK_WIN_AVG = 10,
+  HDK_WIN_MIN = 11, HDK_WIN_MAX = 12, HDK_WIN_SUM = 13, HDK_WIN_COUNT = 14
+} hdk_hip_window_kind;
+
+typedef enum hdk_hip_window_frame { HDK_FRAME_ROWS = 0, HDK_FRAME_RANGE = 1, HDK_FRAME_PARTITION = 2 } hdk_hip_window_frame;
+
+typedef struct hdk_hip_window_out {
+  int32_t col;        /* input column; ignored for the ranking kinds and for COUNT(*) (col < 0) */
+  uint8_t kind;       /* hdk_hip_window_kind */
+  uint8_t frame;      /* hdk_hip_window_frame: read by the aggregates and by LAST_VALUE */
+  uint8_t is_fp;      /* words are doubles (SUM / MIN / MAX / AVG as doubles); else int64 */
+  uint8_t nullable;   /* 0: null_bits is an ordinary value */
+  int64_t null_bits;  /* the input column's in-band NULL, as in hdk_hip_group_out */
+  int64_t param;      /* NTILE: n; LAG / LEAD: k */
+} hdk_hip_window_out;
+
+size_t hdk_hip_window_columns_workspace_bytes(uint64_t num_rows, int32_t num_outs);
+int32_t hdk_hip_window_columns(const int64_t* cols, uint64_t capacity, int32_t num_cols, uint64_t num_rows,
+                               const int32_t* part_cols, int32_t num_part, const int32_t* order_cols, int32_t num_order,
+                               const hdk_hip_window_out* outs, int32_t num_outs, int64_t* out_cols, uint64_t out_capacity,
+                               void* workspace, size_t workspace_bytes, int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Environment switches (MI355X addition; no reference counterpart: the reference's knobs are Config fields,
  * Shared/Config.h).  libhdk_hip.so reads its HDK_HIP_* variables (tests and A/B measurements, none needed
  * in production) ONCE per process, at the first launch that asks for one -- never per launch, so a host that calls
