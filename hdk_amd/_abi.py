@@ -21,6 +21,10 @@ MAX_GROUP_KEYS = 8
 MAX_GROUP_OUTS = 16
 MAX_WINDOW_KEYS = 8
 MAX_WINDOW_OUTS = 8
+MAX_PROJECT_OUTS = 8
+MAX_PROJECT_OPS = 48
+MAX_PROJECT_STACK = 6
+MAX_PROJECT_INPUTS = 8
 SORT_NO_SELECT = 1  # hdk_hip_sort_columns flags
 F_AND, F_OR, F_NOT = 64, 65, 66
 PLAN_ABI = 4
@@ -69,6 +73,10 @@ AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_AVG, AGG_ID, AGG_SINGLE_VALUE = 0, 1, 
 (WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_PERCENT_RANK, WIN_CUME_DIST, WIN_NTILE, WIN_LAG, WIN_LEAD, WIN_FIRST_VALUE,
  WIN_LAST_VALUE, WIN_AVG, WIN_MIN, WIN_MAX, WIN_SUM, WIN_COUNT) = range(15)
 FRAME_ROWS, FRAME_RANGE, FRAME_PARTITION = 0, 1, 2
+# hdk_hip_project_code and hdk_hip_project_flag
+(P_PUSH_COL, P_PUSH_INT, P_PUSH_FP, P_PUSH_NULL_INT, P_PUSH_NULL_FP, P_ADD_I, P_SUB_I, P_MUL_I, P_DIV_I, P_MOD_I, P_ADD_F,
+ P_SUB_F, P_MUL_F, P_DIV_F, P_CAST_I2F, P_CAST_F2I, P_CMP_I, P_CMP_F, P_AND, P_OR, P_NOT, P_IS_NULL, P_SELECT) = range(1, 24)
+P_FLAG_NULLABLE, P_FLAG_FP = 1, 2
 JC_SMALL_DATE, JC_SIGNED, JC_UNSIGNED, JC_DOUBLE = 0, 1, 2, 3
 (KP_COL_BUFFERS, KP_NUM_FRAGMENTS, KP_LITERALS, KP_NUM_ROWS, KP_FRAG_ROW_OFFSETS, KP_MAX_MATCHED,
  KP_TOTAL_MATCHED, KP_INIT_AGG_VALS, KP_GROUPBY_BUF, KP_ERROR_CODE, KP_NUM_TABLES,
@@ -186,6 +194,20 @@ class WindowOut(C.Structure):
     the word equals null_bits."""
     _fields_ = [("col", C.c_int32), ("kind", C.c_uint8), ("frame", C.c_uint8), ("is_fp", C.c_uint8), ("nullable", C.c_uint8),
                 ("null_bits", C.c_int64), ("param", C.c_int64)]
+
+
+class ProjectOp(C.Structure):
+    """hdk_hip_project_op: one postfix op of hdk_hip_project_columns.  flags: P_FLAG_* for P_PUSH_COL, the CMP_* code for
+    P_CMP_I / P_CMP_F; imm: the column's in-band NULL, or the literal (a double's bits for P_PUSH_FP)."""
+    _fields_ = [("code", C.c_uint8), ("check_width", C.c_uint8), ("flags", C.c_uint8), ("pad_", C.c_uint8), ("col", C.c_uint32),
+                ("imm", C.c_int64)]
+
+
+class ProjectOut(C.Structure):
+    """hdk_hip_project_out: one output of hdk_hip_project_columns: ops[first_op .. first_op + num_ops) leave its value, a
+    NULL result stores null_bits."""
+    _fields_ = [("first_op", C.c_int32), ("num_ops", C.c_int32), ("is_fp", C.c_uint8), ("nullable", C.c_uint8),
+                ("pad_", C.c_uint8 * 6), ("null_bits", C.c_int64)]
 
 
 class KernelOptions(C.Structure):

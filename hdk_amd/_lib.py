@@ -85,6 +85,8 @@ SIGNATURES = {
     "hdk_hip_window_columns_workspace_bytes": (sz, [C.c_uint64, i32]),
     "hdk_hip_window_columns": (i32, [v, C.c_uint64, i32, C.c_uint64, C.POINTER(i32), i32, C.POINTER(i32), i32,
                                      C.POINTER(A.WindowOut), i32, v, C.c_uint64, v, sz, i32, v]),
+    "hdk_hip_project_columns": (i32, [v, C.c_uint64, i32, C.c_uint64, C.POINTER(A.ProjectOp), i32, C.POINTER(A.ProjectOut), i32,
+                                      v, C.c_uint64, v, i32, v]),
     "hdk_hip_exchange_shape_for": (i32, [C.POINTER(A.Plan), C.POINTER(A.KernelOptions), i32, u32, i32,
                                          C.POINTER(A.ExchangeShape)]),
     "hdk_hip_scatter_to_owners": (i32, [C.POINTER(A.Plan), C.POINTER(v), C.POINTER(A.KernelOptions),
@@ -120,6 +122,8 @@ EXTRA_SIGNATURES = {
     "hdk_hip_sizeof_kernel_options": (sz, []),
     "hdk_hip_sizeof_group_out": (sz, []),
     "hdk_hip_sizeof_window_out": (sz, []),
+    "hdk_hip_sizeof_project_op": (sz, []),
+    "hdk_hip_sizeof_project_out": (sz, []),
 }
 
 

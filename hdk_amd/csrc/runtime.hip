@@ -474,5 +474,7 @@ size_t hdk_hip_sizeof_device_properties(void) { return sizeof(hdk_hip_device_pro
 size_t hdk_hip_sizeof_kernel_options(void) { return sizeof(hdk_hip_kernel_options); }
 size_t hdk_hip_sizeof_group_out(void) { return sizeof(hdk_hip_group_out); }
 size_t hdk_hip_sizeof_window_out(void) { return sizeof(hdk_hip_window_out); }
+size_t hdk_hip_sizeof_project_op(void) { return sizeof(hdk_hip_project_op); }
+size_t hdk_hip_sizeof_project_out(void) { return sizeof(hdk_hip_project_out); }
 
 }  // extern "C"

@@ -25,8 +25,8 @@ from .hip_mgr import DeviceBuffer, HipMgr
 from .ir import QueryMustRunOnCpu, QueryUnit
 from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, GROUP_KINDS, ColumnDesc, CompiledPlan, Having, columnar_init_vals,
                    compact_init_vals, compile_query, describe_columns, eff_key_count, has_count_distinct, regroup_columns,
-                   group_windows, resolve_having, resolve_having_columns, resolve_order_by, resolve_window_columns,
-                   split_count_distinct)
+                   group_windows, resolve_having, resolve_having_columns, resolve_order_by, resolve_select_columns,
+                   resolve_window_columns, split_count_distinct, split_project_calls)
 from .storage import ArrowStorage
 
 
@@ -391,6 +391,52 @@ class DeviceColumns:
                     cols.free()
             cols = nxt
         return cols
+
+    def project(self, outs) -> "DeviceColumns":
+        """Computed columns on the device (hdk_hip_project_columns; the reference's project step over the previous step's
+        result) -> a new DeviceColumns that carries the new schema and ONLY the listed columns, every input row once in
+        this object's order; this object stays valid.  `outs`: ir.Proj items over ir.TargetRef (a column by index or name),
+        Lit, BinOp, Cast, Case and the conditions Cmp / And / Or / Not / IsNull; a bare TargetRef copies its column
+        (plan.resolve_select_columns has the rules for type, name and nullability).  One exactly sized block; a select list
+        beyond one call's outs, ops or input columns goes through further calls that write into the same block.  One
+        stream synchronisation, after which the error word is read: a division by zero or an overflow that a row raised
+        frees the block and raises HdkHipError with the reference's code."""
+        programs, descs = resolve_select_columns(self.columns(), outs)
+        out = DeviceColumns(self.compiled, self.mgr, self.device_id, None, 0, 0, self.error_code, descs)
+        n = self.num_rows
+        if n == 0:
+            return out
+        if self.block is None or not self.block.ptr:
+            raise ValueError("the columns have been freed")
+        calls = split_project_calls(programs)
+        block = self.mgr.alloc(len(programs) * n * 8, self.device_id)
+        try:
+            errors = self.mgr.alloc(4 * len(calls), self.device_id)  # one error word per call
+            try:
+                for c, (j0, count) in enumerate(calls):
+                    part = programs[j0:j0 + count]
+                    ops = (A.ProjectOp * sum(len(p.ops) for p in part))()
+                    parr = (A.ProjectOut * count)()
+                    at = 0
+                    for j, p in enumerate(part):
+                        parr[j] = A.ProjectOut(at, len(p.ops), int(p.is_fp), int(p.nullable), (C.c_uint8 * 6)(),
+                                               A.to_i64(p.null_bits))
+                        for code, width, flags, col, imm in p.ops:
+                            ops[at] = A.ProjectOp(code, width, flags, 0, col, A.to_i64(imm))
+                            at += 1
+                    check(lib().hdk_hip_project_columns(self.block.ptr, self.capacity, self.num_cols, n, ops, at, parr, count,
+                                                        block.ptr + j0 * n * 8, n, errors.ptr + 4 * c, self.device_id, None))
+                self.mgr.synchronizeStream(self.device_id)
+                err = int(self.mgr.to_host(errors.ptr, 4 * len(calls), self.device_id, np.int32).max())
+            finally:
+                errors.free()
+            if err:
+                raise HdkHipError(err, f"device error code {err} (QE/Execute.h:1019-1031)")
+        except Exception:
+            block.free()
+            raise
+        out.block, out.capacity, out.num_rows = block, n, n
+        return out
 
     def free(self):
         if self.block is not None:
@@ -868,6 +914,8 @@ class Executor:
         sq = q.query if isinstance(q, CompiledPlan) else q
         if sq.windows and result == "buffer":
             raise ValueError("windows need result='columns': they read the dense result columns, not a hash-table buffer")
+        if sq.select and result == "buffer":
+            raise ValueError("select needs result='columns': it computes over the dense result columns, not a hash-table buffer")
         if has_count_distinct(sq):
             if result == "buffer":
                 raise ValueError("count_distinct needs result='columns': it regroups the dense result columns of an inner "
@@ -902,10 +950,16 @@ class Executor:
                         finally:
                             cols.free()
                         cols = windowed
+                    if sq.select:  # after the windows, whose columns it may read; the SortInfo names ITS columns
+                        try:
+                            projected = cols.project(sq.select)
+                        finally:
+                            cols.free()
+                        cols = projected
                     if not sorts:
                         return cols
                     try:
-                        return cols.sort(sq.order_by if sq.windows else step.cp.order_by, sq.limit, sq.offset)
+                        return cols.sort(sq.order_by if sq.windows or sq.select else step.cp.order_by, sq.limit, sq.offset)
                     finally:
                         cols.free()
                 return step.run()
@@ -940,6 +994,12 @@ class Executor:
             finally:
                 out.free()
             out = windowed
+        if rg.select:
+            try:
+                projected = out.project(rg.select)
+            finally:
+                out.free()
+            out = projected
         if not (rg.order_by or rg.limit is not None or rg.offset):
             return out
         try:

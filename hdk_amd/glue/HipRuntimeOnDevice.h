@@ -266,4 +266,19 @@ inline void window_columns_on_device(const int64_t* cols, const size_t capacity,
                                workspace_bytes, device_id, nullptr));
 }
 
+// The project step for a result whose dense columns are on the device: computed columns over the previous step's
+// materialised result, with the reference's nullable arithmetic, checked + - *, division guard, casts, comparisons,
+// three-valued logic and CASE (hdk_hip_project_columns in hdk_hip.h has the op set).  `ops` holds the postfix programs of
+// the `num_outs` outs (hdk_hip_project_out names each out's range); out j lands at out_cols + j * out_capacity, num_rows
+// words in input row order.  `error_code` is the step's ERROR_CODE word in device memory: the call stores 0 and rows that
+// raise leave ERR_DIV_BY_ZERO / ERR_OVERFLOW_OR_UNDERFLOW there, to be read once the stream has drained, as after a
+// kernel launch.  No workspace.  Asynchronous on the device's stream: the host never waits.
+inline void project_columns_on_device(const int64_t* cols, const size_t capacity, const int num_cols, const size_t num_rows,
+                                      const hdk_hip_project_op* ops, const int num_ops, const hdk_hip_project_out* outs,
+                                      const int num_outs, int64_t* out_cols, const size_t out_capacity, int32_t* error_code,
+                                      const int device_id) {
+  check(hdk_hip_project_columns(cols, static_cast<uint64_t>(capacity), num_cols, static_cast<uint64_t>(num_rows), ops, num_ops, outs,
+                                num_outs, out_cols, static_cast<uint64_t>(out_capacity), error_code, device_id, nullptr));
+}
+
 }  // namespace hip_rt

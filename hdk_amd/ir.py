@@ -123,7 +123,8 @@ class Lit(Expr):
 class TargetRef(Expr):
     """A target of the same step, by 0-based index or output name: what a HAVING comparison reads (the reference's
     filter step over the previous step's result names that result's columns).  Valid only inside QueryUnit.having:
-    compile_query raises a ValueError for one in quals, groupby, targets or join keys."""
+    compile_query raises a ValueError for one in quals, groupby, targets or join keys.  Inside QueryUnit.select it names a
+    column of the result that the projection reads: a target or a window column."""
     target: Union[int, str]
 
 
@@ -175,7 +176,22 @@ class Not:
     arg: "Cond"
 
 
-Cond = Union[Cmp, And, Or, Not]
+@dataclass(frozen=True)
+class IsNull:
+    """arg IS NULL: a condition that is never NULL itself.  Valid inside QueryUnit.select (DeviceColumns.project)."""
+    arg: Expr
+
+
+Cond = Union[Cmp, And, Or, Not, IsNull]
+
+
+@dataclass(frozen=True)
+class Case(Expr):
+    """CASE WHEN cond THEN expr [WHEN ...] [ELSE else_] END (hdk::ir::CaseExpr): the first `whens` pair whose condition is
+    TRUE gives the value; a FALSE or NULL condition moves on; without `else_` (or with Lit(None) for it) the rest is NULL.
+    A branch that is Lit(None) is a NULL of the other branches' type.  Valid inside QueryUnit.select."""
+    whens: Sequence  # of (Cond, Expr)
+    else_: Optional[Expr] = None
 
 
 @dataclass(frozen=True)
@@ -281,3 +297,7 @@ class QueryUnit:
     # window functions over the result columns, applied on the device after HAVING and before order_by / limit / offset
     # (result="columns"): each adds a column after the targets, in this order; order_by may name one
     windows: List[Window] = field(default_factory=list)
+    # the final projection: Proj(expr, name) items over the result columns (targets and window columns, by TargetRef), applied
+    # on the device after HAVING and the windows and before order_by / limit / offset (result="columns"), whose entries then
+    # name the PROJECTED columns.  The result holds these columns only.  Empty: every column as it is
+    select: List["Proj"] = field(default_factory=list)

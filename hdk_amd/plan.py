@@ -10,6 +10,7 @@ Host-side mirror of what the reference does between `RelAlgExecutionUnit` and th
 Instead of emitting LLVM IR the work unit is pattern-matched into `hdk_hip_plan`; shapes outside the
 fixed kernel library raise QueryMustRunOnCpu (reference RelAlgExecutor.cpp:183-192 retry).
 """
+import dataclasses
 import math
 import struct
 from dataclasses import dataclass, field
@@ -546,6 +547,242 @@ def group_windows(windows) -> List[Tuple[tuple, tuple, List[int]]]:
         else:
             groups.append((key[0], key[1], [i]))
     return groups
+
+
+def resolve_unit_select(cols: List[ColumnDesc], windows, select, order_by=()) -> List[ColumnDesc]:
+    """A unit's select list checked against the columns it will meet: `cols` followed by one column per window, named and
+    grouped as DeviceColumns.windows does; the order entries against the projected columns.  -> the projected schema.
+    Raises what resolve_window_columns, resolve_select_columns and resolve_order_by raise."""
+    cols = list(cols)
+    base = len(cols)
+    windows = [dataclasses.replace(w, name=w.name or f"{w.kind}_{base + i}") for i, w in enumerate(windows)]
+    for partition_by, order, idx in group_windows(windows):
+        cols += resolve_window_columns(cols, partition_by, order, [windows[i] for i in idx])[3]
+    _, descs = resolve_select_columns(cols, select)
+    resolve_order_by(descs, len(descs), list(order_by))
+    return descs
+
+
+@dataclass(frozen=True)
+class ProjectProgram:
+    """One resolved out of a projection: the postfix ops of hdk_hip_project_columns as (code, check_width, flags, column,
+    imm) tuples, the out's is_fp / nullable / null_bits, the deepest value stack the ops need and the distinct input
+    columns they read."""
+    ops: tuple
+    is_fp: bool
+    nullable: bool
+    null_bits: int
+    depth: int
+    inputs: tuple
+
+
+_P_PUSHES = (A.P_PUSH_COL, A.P_PUSH_INT, A.P_PUSH_FP, A.P_PUSH_NULL_INT, A.P_PUSH_NULL_FP)
+_P_UNARY = (A.P_CAST_I2F, A.P_CAST_F2I, A.P_NOT, A.P_IS_NULL)
+_P_ARITH = {"+": (A.P_ADD_I, A.P_ADD_F), "-": (A.P_SUB_I, A.P_SUB_F), "*": (A.P_MUL_I, A.P_MUL_F),
+            "/": (A.P_DIV_I, A.P_DIV_F), "%": (A.P_MOD_I, None)}
+
+
+def project_stack_depth(ops) -> int:
+    """The deepest value stack a postfix program of hdk_hip_project_columns ops reaches."""
+    depth = deepest = 0
+    for op in ops:
+        code = op[0]
+        depth += 1 if code in _P_PUSHES else 0 if code in _P_UNARY else -2 if code == A.P_SELECT else -1
+        deepest = max(deepest, depth)
+    return deepest
+
+
+def resolve_select_columns(cols: List[ColumnDesc], outs) -> Tuple[List[ProjectProgram], List[ColumnDesc]]:
+    """DeviceColumns.project's select list resolved against the columns `cols`: -> (one ProjectProgram per out, the
+    ColumnDesc of every out: the schema of the projected result).  `outs`: ir.Proj items (a bare expression will do) over
+    ir.TargetRef (a column by index or name), Lit, BinOp, Cast, Case and, as CASE conditions, Cmp / And / Or / Not / IsNull.
+    Typing is _Binder.type_of's with ColumnDesc.type for the leaves: int op int is BIGINT, any fp operand makes a DOUBLE
+    (the int side is cast), the result is nullable if an operand is; CASE is nullable if a branch is or there is no ELSE.
+    + - * are checked in the wider operand's SQL type (_sql_int_width's rule).  Int outs are Type("int", 8) with NULL
+    INT64_MIN, fp outs DOUBLE with NULL_DOUBLE; an out that is a bare TargetRef is a pass-through and keeps the column's
+    whole ColumnDesc (dictionary, scale) but for its name and place.  An out without a name is called after its column, or
+    expr_<index>.  A ValueError: an unknown column or operator, a name taken twice.  What the library cannot express must
+    run on the CPU: a decimal with a scale, a dictionary-encoded column or a date inside an expression, fp modulo, a cast
+    to anything but int / fp, a stack deeper than MAX_PROJECT_STACK, more than MAX_PROJECT_INPUTS distinct columns or more
+    than MAX_PROJECT_OPS ops in one out."""
+    from .ir import Case, IsNull, Proj
+    by_name = {c.name: i for i, c in enumerate(cols)}
+
+    def column(e: TargetRef) -> int:
+        t = e.target
+        if isinstance(t, str):
+            if t not in by_name:
+                raise ValueError(f"select names no column: {t!r}")
+            return by_name[t]
+        if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not 0 <= int(t) < len(cols):
+            raise ValueError(f"select column index {t!r} outside 0..{len(cols) - 1}")
+        return int(t)
+
+    def is_null_lit(e) -> bool:
+        return e is None or (isinstance(e, Lit) and e.value is None)
+
+    # every emitter appends to `ops` and returns (is_fp, nullable, SQL int width or 0)
+    def to_fp(ops, fp):
+        if not fp:
+            ops.append((A.P_CAST_I2F, 0, 0, 0, 0))
+
+    def value(ops, e):
+        if isinstance(e, TargetRef):
+            t = column(e)
+            c = cols[t]
+            if c.dictionary is not None or c.type.kind == "dict":
+                raise QueryMustRunOnCpu(f"a dictionary-encoded column ({c.name}) inside an expression: it holds string ids")
+            if c.type.kind == "decimal" or c.scale:
+                raise QueryMustRunOnCpu(f"a decimal column ({c.name}) inside an expression: it holds scaled values")
+            if c.type.kind == "date":
+                raise QueryMustRunOnCpu(f"date arithmetic ({c.name}) is outside the fixed kernel library")
+            flags = (A.P_FLAG_NULLABLE if c.nullable else 0) | (A.P_FLAG_FP if c.is_fp else 0)
+            ops.append((A.P_PUSH_COL, 0, flags, t, A.to_i64(c.null_bits) if c.nullable else 0))
+            return bool(c.is_fp), bool(c.nullable), 0 if c.is_fp else int(c.type.size)
+        if isinstance(e, Lit):
+            v = e.value
+            if isinstance(v, (bool, np.bool_)):
+                v = int(v)
+            if isinstance(v, (float, np.floating)):
+                ops.append((A.P_PUSH_FP, 0, 0, 0, _dbits(float(v))))
+                return True, False, 0
+            if not isinstance(v, (int, np.integer)) or not -2**63 <= int(v) < 2**63:
+                raise QueryMustRunOnCpu(f"literal {v!r} is no int64 or double")
+            ops.append((A.P_PUSH_INT, 0, 0, 0, int(v)))
+            return False, False, 4 if -(2**31) <= int(v) < 2**31 else 8
+        if isinstance(e, BinOp):
+            if e.op not in _P_ARITH:
+                raise ValueError(f"unknown arithmetic operator {e.op!r}")
+            lhs: list = []
+            l_fp, l_nullable, lw = value(lhs, e.lhs)
+            rhs: list = []
+            r_fp, r_nullable, rw = value(rhs, e.rhs)
+            fp = l_fp or r_fp
+            if fp:
+                if e.op == "%":
+                    raise QueryMustRunOnCpu("fp modulo")
+                to_fp(lhs, l_fp)
+                to_fp(rhs, r_fp)
+            w = 0 if fp else max(lw, rw)
+            ops.extend(lhs + rhs)
+            ops.append((_P_ARITH[e.op][int(fp)], w if e.op in "+-*" else 0, 0, 0, 0))
+            return fp, l_nullable or r_nullable, w
+        if isinstance(e, Cast):
+            fp, nullable, w = value(ops, e.arg)
+            if e.to.is_fp:
+                to_fp(ops, fp)
+                return True, nullable, 0
+            if e.to.kind != "int":
+                raise QueryMustRunOnCpu(f"unsupported cast to {e.to}")
+            if fp:
+                ops.append((A.P_CAST_F2I, 0, 0, 0, 0))
+            return False, nullable, 8  # (casts give BIGINT)
+        if isinstance(e, Case):
+            whens = list(e.whens)
+            if not whens:
+                raise ValueError("a CASE needs at least one WHEN")
+            branches = [x for _, x in whens] + [e.else_]
+            typed = [x for x in branches if not is_null_lit(x)]
+            if not typed:
+                raise ValueError("every branch of the CASE is NULL: it has no type")
+            parts = [None if is_null_lit(x) else [] for x in branches]
+            infos = [None if p is None else value(p, x) for p, x in zip(parts, branches)]
+            fp = any(i[0] for i in infos if i)
+            nullable = any(i is None or i[1] for i in infos)
+            w = 0 if fp else max(i[2] for i in infos if i)
+            for k, (p, i) in enumerate(zip(parts, infos)):
+                if p is None:
+                    parts[k] = [(A.P_PUSH_NULL_FP if fp else A.P_PUSH_NULL_INT, 0, 0, 0, 0)]
+                elif fp:
+                    to_fp(p, i[0])
+            for (c, _), p in zip(whens, parts):  # cond then cond then ... else SELECT SELECT ...
+                cond(ops, c)
+                ops.extend(p)
+            ops.extend(parts[-1])
+            ops.extend([(A.P_SELECT, 0, 0, 0, 0)] * len(whens))
+            return fp, nullable, w
+        if isinstance(e, ColRef):
+            raise ValueError(f"{e!r}: a projection reads result columns, named by ir.TargetRef")
+        raise QueryMustRunOnCpu(f"unsupported expression {e!r}")
+
+    def cond(ops, c):
+        if isinstance(c, Cmp):
+            if c.op not in _CMP:
+                raise ValueError(f"unknown comparison operator {c.op!r}")
+            lhs: list = []
+            l_fp, _, _ = value(lhs, c.lhs)
+            rhs: list = []
+            r_fp, _, _ = value(rhs, c.rhs)
+            fp = l_fp or r_fp
+            if fp:
+                to_fp(lhs, l_fp)
+                to_fp(rhs, r_fp)
+            ops.extend(lhs + rhs)
+            ops.append((A.P_CMP_F if fp else A.P_CMP_I, 0, _CMP[c.op], 0, 0))
+        elif isinstance(c, (And, Or)):
+            cond(ops, c.lhs)
+            cond(ops, c.rhs)
+            ops.append((A.P_AND if isinstance(c, And) else A.P_OR, 0, 0, 0, 0))
+        elif isinstance(c, Not):
+            cond(ops, c.arg)
+            ops.append((A.P_NOT, 0, 0, 0, 0))
+        elif isinstance(c, IsNull):
+            value(ops, c.arg)
+            ops.append((A.P_IS_NULL, 0, 0, 0, 0))
+        else:
+            raise QueryMustRunOnCpu(f"unsupported condition {c!r}")
+
+    outs = list(outs)
+    if not outs:
+        raise ValueError("a projection needs at least one out")
+    programs, descs = [], []
+    for j, o in enumerate(outs):
+        expr, name = (o.expr, o.name) if isinstance(o, Proj) else (o, None)
+        if isinstance(expr, (str, int, np.integer)) and not isinstance(expr, bool):
+            expr = TargetRef(expr)
+        if isinstance(expr, TargetRef):  # a pass-through: the word is copied unexamined, whatever its type
+            t = column(expr)
+            src = cols[t]
+            flags = (A.P_FLAG_NULLABLE if src.nullable else 0) | (A.P_FLAG_FP if src.is_fp else 0)
+            programs.append(ProjectProgram(((A.P_PUSH_COL, 0, flags, t, A.to_i64(src.null_bits) if src.nullable else 0),),
+                                           bool(src.is_fp), bool(src.nullable), A.to_i64(src.null_bits), 1, (t,)))
+            descs.append(dataclasses.replace(src, name=name or src.name, target_idx=j))
+            continue
+        ops: list = []
+        fp, nullable, _ = value(ops, expr)
+        depth = project_stack_depth(ops)
+        inputs = tuple(dict.fromkeys(op[3] for op in ops if op[0] == A.P_PUSH_COL))
+        if depth > A.MAX_PROJECT_STACK:
+            raise QueryMustRunOnCpu("select expression %d needs a value stack of %d, at most %d" % (j, depth, A.MAX_PROJECT_STACK))
+        if len(inputs) > A.MAX_PROJECT_INPUTS:
+            raise QueryMustRunOnCpu("select expression %d reads %d distinct columns, at most %d"
+                                    % (j, len(inputs), A.MAX_PROJECT_INPUTS))
+        if len(ops) > A.MAX_PROJECT_OPS:
+            raise QueryMustRunOnCpu("select expression %d is too long for the fixed kernel library (%d ops, at most %d)"
+                                    % (j, len(ops), A.MAX_PROJECT_OPS))
+        null_bits = A.to_i64(A.NULL_DOUBLE_BITS) if fp else A.NULL_BIGINT
+        programs.append(ProjectProgram(tuple(ops), fp, nullable, null_bits, depth, inputs))
+        descs.append(ColumnDesc(name or f"expr_{j}", fp, nullable, null_bits, Type("fp" if fp else "int", 8, nullable), j, "agg",
+                                "expr"))
+    names = [d.name for d in descs]
+    if len(set(names)) != len(names):
+        raise ValueError(f"a select column's name is taken: {names}")
+    return programs, descs
+
+
+def split_project_calls(programs: List[ProjectProgram]) -> List[Tuple[int, int]]:
+    """Consecutive outs as the calls of hdk_hip_project_columns that take them: -> [(first out, outs)], each within
+    MAX_PROJECT_OUTS outs, MAX_PROJECT_OPS ops and MAX_PROJECT_INPUTS distinct input columns."""
+    calls, first, nops, inputs = [], 0, 0, set()
+    for j, p in enumerate(programs):
+        if j > first and (j - first == A.MAX_PROJECT_OUTS or nops + len(p.ops) > A.MAX_PROJECT_OPS
+                          or len(inputs | set(p.inputs)) > A.MAX_PROJECT_INPUTS):
+            calls.append((first, j - first))
+            first, nops, inputs = j, 0, set()
+        nops += len(p.ops)
+        inputs |= set(p.inputs)
+    calls.append((first, len(programs) - first))
+    return calls
 
 
 @dataclass
@@ -1112,6 +1349,8 @@ def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
             raise QueryMustRunOnCpu("ORDER BY / LIMIT / OFFSET on a projection: it has no dense device columns")
         if q.having:
             raise QueryMustRunOnCpu("HAVING on a step that is not a group-by: a projection has no dense device columns")
+        if q.select:
+            raise QueryMustRunOnCpu("select on a step that is not a group-by: a projection has no dense device columns")
         return compile_projection(storage, q)
     if any(isinstance(t, Proj) for t in q.targets):
         raise QueryMustRunOnCpu("mixing projections and aggregates")
@@ -1435,16 +1674,22 @@ def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
     if _has_sort_info(q):
         if kind == A.Q_NON_GROUPED:
             raise QueryMustRunOnCpu("ORDER BY / LIMIT / OFFSET on a non-grouped query: it has no dense device columns")
-        if not q.windows:  # (with windows the entries may name a window column: DeviceColumns.sort resolves them)
+        # (with windows the entries may name a window column, with a select list they name the projected columns:
+        # DeviceColumns.sort resolves them)
+        if not q.windows and not q.select:
             order_by = resolve_order_by(out_cols, int(p.num_targets), q.order_by)
     if q.windows and kind == A.Q_NON_GROUPED:
         raise QueryMustRunOnCpu("window functions on a non-grouped query: it has no dense device columns")
+    if q.select and kind == A.Q_NON_GROUPED:
+        raise QueryMustRunOnCpu("select on a non-grouped query: it has no dense device columns")
     cp = CompiledPlan(plan=p, query=q, init_vals=np.array(init_vals, dtype=np.int64),
                       slot_widths=slot_widths, input_cols=list(b.cols),
                       inner_tables=[t.name for t in b.inner], join_infos=join_infos,
                       out_cols=out_cols, key_types=key_types, buffer_bytes=buffer_bytes,
                       key_ranges=key_ranges, order_by=order_by)
     cp.having = resolve_having(cp, q.having)
+    if q.select:  # validated here, as HAVING is; DeviceColumns.project resolves it again against the columns it meets
+        resolve_unit_select(describe_columns(cp), q.windows, q.select, q.order_by)
     return cp
 
 
@@ -1553,6 +1798,7 @@ class Regroup:
     limit: Optional[int]
     offset: int
     windows: list = field(default_factory=list)
+    select: list = field(default_factory=list)
 
 
 def has_count_distinct(q: QueryUnit) -> bool:
@@ -1598,5 +1844,6 @@ def split_count_distinct(q: QueryUnit) -> Tuple[QueryUnit, Regroup]:
         else:
             raise ValueError(f"unknown aggregate {t.kind!r}")
     inner = dataclasses.replace(q, groupby=list(q.groupby) + [arg], targets=inner_targets, order_by=[], limit=None, offset=0,
-                                having=[], windows=[])
-    return inner, Regroup(list(range(nk)), outs, list(q.having), list(q.order_by), q.limit, q.offset, list(q.windows))
+                                having=[], windows=[], select=[])
+    return inner, Regroup(list(range(nk)), outs, list(q.having), list(q.order_by), q.limit, q.offset, list(q.windows),
+                          list(q.select))

@@ -856,6 +856,98 @@ int32_t hdk_hip_window_columns(const int64_t* cols, uint64_t capacity, int32_t n
                                void* workspace, size_t workspace_bytes, int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Projection over dense result columns on the device: computed columns, one word per input row and output.
+ * The device form, for a result whose columns sit in HBM, of the reference's project step over the previous step's
+ * materialised result: its nullable arithmetic (DEF_ARITH_NULLABLE*, omniscidb/QueryEngine/RuntimeFunctions.cpp:49-80) with
+ * the checked + - * and the division guard of QE/ArithmeticIR.cpp:277-634, the casts (:311-345), DEF_CMP_NULLABLE*
+ * (:83-117), logical_not / logical_and / logical_or (:355-384) and CASE (codegenCase, QE/CaseIR.cpp).
+ * Input: `num_cols` columns of `num_rows` 8-byte words, column t at cols + t * capacity, NULLs in band -- what the other
+ * *_columns calls write.
+ * Output: out j (of `num_outs`, 1..HDK_HIP_MAX_PROJECT_OUTS) at out_cols + j * out_capacity: exactly `num_rows` words in
+ * input row order.  Nothing at or beyond row num_rows and nothing outside the num_outs columns is written; the input is
+ * not modified; no two of cols, out_cols and error_code_dev may overlap.
+ * A PROGRAM is a postfix sequence of typed ops over a value stack; out j owns ops[first_op .. first_op + num_ops) and
+ * starts on an empty stack.  A call takes at most HDK_HIP_MAX_PROJECT_OPS ops over all outs, a stack of at most
+ * HDK_HIP_MAX_PROJECT_STACK values and at most HDK_HIP_MAX_PROJECT_INPUTS distinct input columns.  Every stack value is a
+ * 64-bit word, a NULL bit and a pending-error mark; its class -- INT (an int64), FP (a double's bits) or BOOL -- is
+ * static, and the library type-checks every program on the host: mixed arithmetic needs explicit casts.
+ *   HDK_P_PUSH_COL        the word of column `col` (flags: HDK_P_FLAG_FP = the class is FP, else INT; HDK_P_FLAG_NULLABLE =
+ *                         the value is NULL when the word is BIT-EQUAL to imm, the rule of hdk_hip_filter_columns)
+ *   HDK_P_PUSH_INT / _FP  imm, an int64 / the bits of a double; never NULL
+ *   HDK_P_PUSH_NULL_INT / _FP   a NULL of that class
+ *   HDK_P_ADD_I SUB_I MUL_I DIV_I MOD_I   b = pop, a = pop, push a op b, as hdk_hip_expr's steps: a NULL operand gives NULL
+ *                         and nothing is checked; + - * wrap, and with check_width 1 / 2 / 4 / 8 (0: unchecked) a result
+ *                         outside the signed type of that many bytes raises HDK_HIP_ERR_OVERFLOW_OR_UNDERFLOW; / and % raise
+ *                         HDK_HIP_ERR_DIV_BY_ZERO on b == 0, truncate towards zero, INT64_MIN / -1 = INT64_MIN, x % -1 = 0
+ *   HDK_P_ADD_F SUB_F MUL_F DIV_F   on doubles, unfused; DIV_F raises HDK_HIP_ERR_DIV_BY_ZERO on b == 0.0 (either zero)
+ *   HDK_P_CAST_I2F        (double) a;  HDK_P_CAST_F2I   (int64_t)(d + (d < 0 ? -0.5 : 0.5)), as HDK_OP_CAST_FP_TO_INT (a
+ *                         NaN or a double outside int64 gives an unspecified word)
+ *   HDK_P_CMP_I / CMP_F   b = pop, a = pop, push the BOOL a <cmp> b with the hdk_hip_cmp in `flags`; NULL when an operand
+ *                         is; doubles compare with the C operators (-0.0 == +0.0; with a NaN only <> is true)
+ *   HDK_P_AND / OR / NOT  three-valued, on BOOLs
+ *   HDK_P_IS_NULL         a BOOL that is never NULL, of a value of any class
+ *   HDK_P_SELECT          e = pop, t = pop, c = pop (a BOOL; t and e of one class): push t when c is TRUE, e when c is FALSE
+ *                         or NULL.  CASE with several WHENs nests it: the ELSE side is the next SELECT
+ * An out must leave exactly one INT (is_fp == 0) or FP (is_fp == 1) value; a NULL result stores null_bits (whatever
+ * `nullable` says: it only describes the column to its next reader).  An out that is a single HDK_P_PUSH_COL is a
+ * pass-through: the word is copied unexamined.
+ * ERRORS ARE LAZY, as the reference's CASE is (a branch is evaluated in its own block): an op that would raise MARKS its
+ * result with the code instead (the marked value itself is unspecified), and an op with a marked operand gives a marked
+ * result (the larger code of two) -- except that HDK_P_SELECT keeps the marks of its condition and of the CHOSEN branch
+ * only, and HDK_P_AND / HDK_P_OR give an unmarked result when an unmarked operand alone decides it (FALSE / TRUE).  A mark
+ * that reaches an out raises.  So CASE WHEN n = 0 THEN NULL ELSE s / n END never raises.  Deviation: the reference's planner
+ * short-circuits AND / OR on one chosen side, and also when that side is NULL; here a NULL side does not hide the other
+ * side's error.
+ * Reporting: the call first stores *error_code_dev = 0 (device memory, stream-ordered); rows that raise then leave the
+ * numerically largest code raised (one atomic max per block that saw any).  After an error the output words are
+ * unspecified.  error_code_dev may be NULL only when no op of the call can raise (no / or %, every check_width 0).
+ * ASYNCHRONOUS on `stream`: one store and one launch; no workspace; the host never waits.
+ * Errors, all found before any device is touched (HDK_HIP_ERR_INVALID_ARG with a message): a NULL cols / ops / outs /
+ * out_cols, num_cols < 1, num_outs outside 1..8, num_ops outside 1..48, an out whose op range is empty or outside the ops, an
+ * unknown code, check_width not 0 / 1 / 2 / 4 / 8, a cmp outside hdk_hip_cmp, stack underflow or a depth above 6, an
+ * operand of the wrong class, an out that leaves no value, more than one, a BOOL or a class that is not its is_fp,
+ * col >= num_cols, more than 8 distinct columns, num_rows >= 2^32, capacity or out_capacity below num_rows, overlapping
+ * blocks, a NULL error_code_dev with a program that can raise.
+ * num_rows == 0: nothing but *error_code_dev is touched.
+ * ---------------------------------------------------------------------------------------- */
+#define HDK_HIP_MAX_PROJECT_OUTS 8
+#define HDK_HIP_MAX_PROJECT_OPS 48
+#define HDK_HIP_MAX_PROJECT_STACK 6
+#define HDK_HIP_MAX_PROJECT_INPUTS 8
+
+typedef enum hdk_hip_project_code {
+  HDK_P_PUSH_COL = 1, HDK_P_PUSH_INT, HDK_P_PUSH_FP, HDK_P_PUSH_NULL_INT, HDK_P_PUSH_NULL_FP,
+  HDK_P_ADD_I, HDK_P_SUB_I, HDK_P_MUL_I, HDK_P_DIV_I, HDK_P_MOD_I,
+  HDK_P_ADD_F, HDK_P_SUB_F, HDK_P_MUL_F, HDK_P_DIV_F,
+  HDK_P_CAST_I2F, HDK_P_CAST_F2I, HDK_P_CMP_I, HDK_P_CMP_F,
+  HDK_P_AND, HDK_P_OR, HDK_P_NOT, HDK_P_IS_NULL, HDK_P_SELECT
+} hdk_hip_project_code;
+enum hdk_hip_project_flag { HDK_P_FLAG_NULLABLE = 1, HDK_P_FLAG_FP = 2 }; /* of HDK_P_PUSH_COL */
+
+typedef struct hdk_hip_project_op {
+  uint8_t code;         /* hdk_hip_project_code */
+  uint8_t check_width;  /* ADD_I / SUB_I / MUL_I: bytes of the checked SQL type, 0 = unchecked */
+  uint8_t flags;        /* PUSH_COL: hdk_hip_project_flag bits; CMP_I / CMP_F: the hdk_hip_cmp */
+  uint8_t pad_;
+  uint32_t col;         /* PUSH_COL: the input column */
+  int64_t imm;          /* PUSH_COL: the column's in-band NULL; PUSH_INT / PUSH_FP: the value */
+} hdk_hip_project_op;
+
+typedef struct hdk_hip_project_out {
+  int32_t first_op;     /* the out's program: ops[first_op .. first_op + num_ops) */
+  int32_t num_ops;
+  uint8_t is_fp;        /* the program leaves an FP value; else an INT */
+  uint8_t nullable;     /* describes the column; a NULL result stores null_bits either way */
+  uint8_t pad_[6];
+  int64_t null_bits;
+} hdk_hip_project_out;
+
+int32_t hdk_hip_project_columns(const int64_t* cols, uint64_t capacity, int32_t num_cols, uint64_t num_rows,
+                                const hdk_hip_project_op* ops, int32_t num_ops, const hdk_hip_project_out* outs,
+                                int32_t num_outs, int64_t* out_cols, uint64_t out_capacity, int32_t* error_code_dev,
+                                int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Environment switches (MI355X addition; no reference counterpart: the reference's knobs are Config fields,
  * Shared/Config.h).  libhdk_hip.so reads its HDK_HIP_* variables (tests and A/B measurements, none needed
  * in production) ONCE per process, at the first launch that asks for one -- never per launch, so a host that calls
