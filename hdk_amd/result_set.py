@@ -27,7 +27,7 @@ def _slot_arrays(cp: CompiledPlan, buf: np.ndarray, entry_count: int) -> List[np
             if not w:  # zero-width slot (projected key of a baseline table): read from the key column
                 out.append(None)
                 continue
-            dt = np.int64 if w == 8 else np.int32
+            dt = {8: np.int64, 4: np.int32, 2: np.int16, 1: np.int8}[w]  # (1 / 2: logical-sized MIN / MAX slots)
             out.append(raw[off:off + entry_count * w].view(dt).astype(np.int64))
         return out
     rb = int(p.row_size_quad) * 8

@@ -492,7 +492,13 @@ int32_t hdk_hip_workspace_size(const hdk_hip_plan* plan, const hdk_hip_kernel_op
 /* Enqueue the scan -> filter -> join-probe -> group/aggregate pass over all fragments described by
  * `params` on `stream` (NULL = the manager's stream for `device_id`).  Asynchronous: results and
  * error codes are complete when the stream is.  The output buffer must already be initialised
- * (hdk_hip_init_*_group_by_buffer, or INIT_AGG_VALS copies for non-grouped out slots). */
+ * (hdk_hip_init_*_group_by_buffer, or INIT_AGG_VALS copies for non-grouped out slots).
+ * The launch MERGES into what the buffer holds, whatever earlier launch (of any route, under any flag or switch) or
+ * hdk_hip_reduce_buffers put it there: groups the launch does not meet stay as they are, COUNT / SUM / AVG add to the stored
+ * value, MIN / MAX combine with it, a slot that still holds its NULL sentinel takes the launch's first value, a new group is
+ * claimed where the reference's probe sequence finds it.  Launches over disjoint row sets into one buffer therefore equal
+ * one launch over all the rows (tests/test_gpu_relaunch.py, every aggregate route).  HDK_HIP_LAUNCH_INIT_OUTPUT is the one
+ * exception: it overwrites the buffer with the empty image first. */
 int32_t hdk_hip_launch(const hdk_hip_plan* plan, int8_t* const params[HDK_KP_COUNT],
                        const hdk_hip_kernel_options* ko, int32_t device_id, void* stream,
                        void* workspace, size_t workspace_bytes);

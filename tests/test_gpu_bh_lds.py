@@ -431,6 +431,10 @@ def test_perfect_hash_benchmark_shape_on_the_packed_kernel(oracle, gpu_executor_
     step.free()
     c1, c2 = res.to_columns(), twice.to_columns()
     assert [2 * x for x in c1["c"]] == c2["c"] and c1["k"] == c2["k"]
+    # ... in every slot: SUM doubles, MIN / MAX / AVG stay, a NULL stays NULL (different rows in the second launch, every
+    # route: tests/test_gpu_relaunch.py)
+    assert [None if x is None else 2 * x for x in c1["s"]] == c2["s"]
+    assert c1["mn"] == c2["mn"] and c1["mx"] == c2["mx"] and c1["a"] == c2["a"]
     # the interpreter and the global-atomics kernels give the identical buffer
     assert_buffers_equal(cp, ex.execute(cp, flags=A.LAUNCH_FORCE_GENERIC).buffer, want)
     assert_buffers_equal(cp, ex.execute(cp, flags=A.LAUNCH_FORCE_GLOBAL_ATOMICS).buffer, want)
