@@ -25,7 +25,7 @@ from .hip_mgr import DeviceBuffer, HipMgr
 from .ir import QueryMustRunOnCpu, QueryUnit
 from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, GROUP_KINDS, ColumnDesc, CompiledPlan, Having, columnar_init_vals,
                    compact_init_vals, compile_query, describe_columns, eff_key_count, has_count_distinct, regroup_columns,
-                   group_windows, resolve_having, resolve_having_columns, resolve_order_by, resolve_select_columns,
+                   group_windows, resolve_having_columns, resolve_order_by, resolve_select_columns,
                    resolve_window_columns, split_count_distinct, split_project_calls)
 from .storage import ArrowStorage
 
@@ -131,53 +131,97 @@ def sized_columns(mgr, device_id, num_targets, worst_rows, call, one_call_bytes,
     return block, capacity, rows
 
 
+def _device_error(err: int) -> HdkHipError:
+    return HdkHipError(err, f"device error code {err} (QE/Execute.h:1019-1031)")
+
+
+def _stage(cols, apply, keep=None):
+    """One stage over dense columns: apply(cols) -> the next columns.  `cols` is handed back whether the stage returned or
+    raised, unless it is `keep`."""
+    try:
+        return apply(cols)
+    finally:
+        if cols is not keep:
+            cols.free()
+
+
+def run_stages(cols, having=None, windows=(), select=(), order_by=(), limit=None, offset=0):
+    """What a unit asks for above its GROUP BY, applied where the columns are: HAVING (a plan.Having or conditions), the
+    window functions, which may read what HAVING kept, the select list, which may read a window column, then the SortInfo,
+    which names the columns it meets.  Consumes `cols`: each stage reads the result of the one before, whose block is handed
+    back, also when a stage raises.  -> the last result; `cols` itself when nothing applies."""
+    if having:
+        cols = _stage(cols, lambda c: c.filter(having))
+    if windows:
+        cols = _stage(cols, lambda c: c.windows(windows))
+    if select:
+        cols = _stage(cols, lambda c: c.project(select))
+    if order_by or limit is not None or offset:
+        cols = _stage(cols, lambda c: c.sort(order_by, limit, offset))
+    return cols
+
+
 class DeviceColumns:
     """Dense result columns in device memory: what hdk_hip_columnarize_result made of a group-by buffer (the device form
     of the reference's ColumnarResults for a ResultSet that lives in HBM).  One 8-byte column per target, rows in entry
     order -- the order ExecutionResult.to_columns() gives.  Owns its device block until free().
-    A result made from a plan reads its columns' description from the plan (result_set.dense_column_null, cp.out_cols).
-    A regrouped result (group_by) no longer has the plan's schema and carries `schema`, one plan.ColumnDesc per column;
-    `compiled` is then the plan it descends from, kept for reference only."""
+    It always carries a schema, one plan.ColumnDesc per column: plan.describe_columns(cp) for a result made from a plan,
+    and what group_by / window / project made of their input's otherwise.  `compiled` is the plan it descends from, kept
+    for reference only."""
 
     def __init__(self, cp: CompiledPlan, mgr: HipMgr, device_id: int, block: Optional[DeviceBuffer], capacity: int,
                  num_rows: int, error_code: int = 0, schema: Optional[List[ColumnDesc]] = None):
         self.compiled, self.mgr, self.device_id = cp, mgr, device_id
         self.block, self.capacity, self.num_rows, self.error_code = block, int(capacity), int(num_rows), error_code
-        self.schema = list(schema) if schema is not None else None
+        self.schema = list(schema) if schema is not None else describe_columns(cp)
 
     @property
     def num_cols(self) -> int:
-        return len(self.schema) if self.schema is not None else int(self.compiled.plan.num_targets)
+        return len(self.schema)
 
     def columns(self) -> List[ColumnDesc]:
-        """One ColumnDesc per column: its own for a regrouped result, derived from the plan otherwise."""
-        return list(self.schema) if self.schema is not None else describe_columns(self.compiled)
+        """One ColumnDesc per column."""
+        return list(self.schema)
 
-    def _like(self, block, capacity, num_rows) -> "DeviceColumns":
-        return DeviceColumns(self.compiled, self.mgr, self.device_id, block, capacity, num_rows, self.error_code, self.schema)
+    def _like(self, block, capacity, num_rows, schema=None) -> "DeviceColumns":
+        """A result of these columns: their schema unless the stage made a new one."""
+        return DeviceColumns(self.compiled, self.mgr, self.device_id, block, capacity, num_rows, self.error_code,
+                             self.schema if schema is None else schema)
 
     def _column_null(self, t: int):
-        """(is_fp, nullable, null_bits) of column t"""
-        if self.schema is None:
-            return result_set.dense_column_null(self.compiled, t)
+        """(is_fp, nullable, null_bits) of column t; t < 0 is no column (COUNT(*)): nothing to compare"""
+        if t < 0:
+            return False, False, 0
         d = self.schema[t]
         return d.is_fp, d.nullable, d.null_bits
+
+    def _block_ptr(self) -> int:
+        if self.block is None or not self.block.ptr:
+            raise ValueError("the columns have been freed")
+        return self.block.ptr
 
     def device_ptr(self, target_idx: int) -> int:
         """Device address of target `target_idx`'s column: num_rows 8-byte values."""
         if not 0 <= target_idx < self.num_cols:
             raise IndexError(target_idx)
-        if self.block is None or not self.block.ptr:
-            raise ValueError("the columns have been freed")
-        return self.block.ptr + target_idx * self.capacity * 8
+        return self._block_ptr() + target_idx * self.capacity * 8
 
     def _is_fp(self, target_idx: int) -> bool:
-        if self.schema is not None:
-            return bool(self.schema[target_idx].is_fp)
-        tg = self.compiled.plan.targets[target_idx]
-        if tg.agg == A.AGG_ID:
-            return bool(self.compiled.key_types[tg.key_idx].is_fp)
-        return tg.agg == A.AGG_AVG or (bool(tg.arg_is_fp) and tg.agg != A.AGG_COUNT)
+        return bool(self.schema[target_idx].is_fp)
+
+    def _order_entries(self, entries):
+        """(column, desc, nulls_first) triples as the library's array"""
+        arr = (A.OrderEntry * len(entries))()
+        for i, (t, desc, nulls_first) in enumerate(entries):
+            is_fp, nullable, null_bits = self._column_null(t)
+            arr[i] = A.OrderEntry(t, int(desc), int(nulls_first), int(is_fp), int(nullable), A.to_i64(null_bits))
+        return arr
+
+    def _copy_rows(self, block: DeviceBuffer, first: int, rows: int):
+        """rows [first, first + rows) of every column into `block`, which holds `rows` rows per column"""
+        for t in range(self.num_cols):
+            self.mgr.copyDeviceToDevice(block.ptr + t * rows * 8, self.device_ptr(t) + first * 8, rows * 8, self.device_id,
+                                        self.device_id)
 
     def to_host(self) -> List[np.ndarray]:
         """One numpy array of num_rows values per target: float64 for fp values (AVG, fp aggregates, fp keys), int64
@@ -194,15 +238,10 @@ class DeviceColumns:
         return [c.view(np.float64) if self._is_fp(t) else c for t, c in enumerate(cols)]
 
     def to_columns(self):
-        dense = [c.view(np.int64) for c in self.to_host()]
-        if self.schema is not None:
-            return result_set.described_to_columns(self.schema, dense)
-        return result_set.dense_to_columns(self.compiled, dense)
+        return result_set.described_to_columns(self.schema, [c.view(np.int64) for c in self.to_host()])
 
     def to_arrow(self):
-        if self.schema is not None:
-            return result_set.described_to_arrow(self.schema, self.to_columns())
-        return result_set.columns_to_arrow(self.compiled, self.to_columns())
+        return result_set.described_to_arrow(self.schema, self.to_columns())
 
     def row_count(self):
         return self.num_rows
@@ -219,7 +258,7 @@ class DeviceColumns:
         nt = self.num_cols
         entries = [e if isinstance(e, tuple) else None for e in order_by]
         if any(e is None for e in entries):
-            entries = resolve_order_by(self.schema if self.schema is not None else self.compiled.out_cols, nt, list(order_by))
+            entries = resolve_order_by(self.schema, nt, list(order_by))
         n = self.num_rows
         after = max(n - int(offset), 0)
         out_rows = after if not limit else min(int(limit), after)
@@ -227,20 +266,14 @@ class DeviceColumns:
             out_rows = 0
         if out_rows == 0:
             return self._like(None, 0, 0)
-        if self.block is None or not self.block.ptr:
-            raise ValueError("the columns have been freed")
+        src = self._block_ptr()
         block = self.mgr.alloc(nt * out_rows * 8, self.device_id)
         try:
             if not entries:
-                for t in range(nt):
-                    self.mgr.copyDeviceToDevice(block.ptr + t * out_rows * 8, self.device_ptr(t) + int(offset) * 8,
-                                                   out_rows * 8, self.device_id, self.device_id)
+                self._copy_rows(block, int(offset), out_rows)
             else:
-                arr = (A.OrderEntry * len(entries))()
-                for i, (t, desc, nulls_first) in enumerate(entries):
-                    is_fp, nullable, null_bits = self._column_null(t)
-                    arr[i] = A.OrderEntry(t, int(desc), int(nulls_first), int(is_fp), int(nullable), A.to_i64(null_bits))
-                check(lib().hdk_hip_sort_columns(self.block.ptr, self.capacity, nt, n, arr, len(entries), int(offset),
+                arr = self._order_entries(entries)
+                check(lib().hdk_hip_sort_columns(src, self.capacity, nt, n, arr, len(entries), int(offset),
                                                  out_rows if limit else 0, A.SORT_NO_SELECT if no_select else 0, block.ptr,
                                                  out_rows, None, None, 0, self.device_id, None))
             self.mgr.synchronizeStream(self.device_id)
@@ -259,19 +292,14 @@ class DeviceColumns:
         num_rows rows per column; above that the passing rows are counted first (out_cols = NULL) and the block holds
         exactly those.  One stream synchronisation per call, to read row_count back."""
         if not isinstance(having, Having):
-            conds = list(having) if isinstance(having, (list, tuple)) else [having]
-            if self.schema is not None:
-                having = resolve_having_columns(self.schema, len(self.schema), self._column_null, conds)
-            else:
-                having = resolve_having(self.compiled, conds)
+            having = resolve_having_columns(self.schema, list(having) if isinstance(having, (list, tuple)) else [having])
         nt = self.num_cols
         n = self.num_rows
         if n == 0 or having is None:
             if having is None and n:
                 return self.sort([])  # no predicate: every row, copied
             return self._like(None, 0, 0)
-        if self.block is None or not self.block.ptr:
-            raise ValueError("the columns have been freed")
+        src = self._block_ptr()
         leaves = (A.HavingLeaf * len(having.leaves))()
         for i, lf in enumerate(having.leaves):
             leaves[i] = A.HavingLeaf(lf.lhs_col, lf.rhs_col, lf.cmp, int(lf.rhs_is_col), int(lf.cmp_fp), int(lf.lhs_is_fp),
@@ -280,7 +308,7 @@ class DeviceColumns:
         ops = (C.c_uint8 * max(len(having.prog), 1))(*having.prog)
 
         def call(out_ptr, capacity, row_count_ptr):
-            check(lib().hdk_hip_filter_columns(self.block.ptr, self.capacity, nt, n, leaves, len(having.leaves), ops,
+            check(lib().hdk_hip_filter_columns(src, self.capacity, nt, n, leaves, len(having.leaves), ops,
                                                len(having.prog), out_ptr, capacity, row_count_ptr, None, None, 0,
                                                self.device_id, None))
 
@@ -299,20 +327,19 @@ class DeviceColumns:
         ADJACENT rows: unless `presorted` says that rows with equal keys already are, a copy sorted by the keys is made
         first (hdk_hip_sort_columns, no limit) and freed afterwards.  Rows come out in that order: ascending by the
         keys, NULLs last.  Sizing as filter(): up to 64 MiB of worst-case output in one call, else count first."""
-        key_cols, spec, descs = regroup_columns(self.columns(), keys, outs)
-        out = DeviceColumns(self.compiled, self.mgr, self.device_id, None, 0, 0, self.error_code, descs)
+        key_cols, spec, descs = regroup_columns(self.schema, keys, outs)
+        out = self._like(None, 0, 0, descs)
         n = self.num_rows
         if n == 0:
             return out
-        if self.block is None or not self.block.ptr:
-            raise ValueError("the columns have been freed")
+        self._block_ptr()
         src = self if presorted else self.sort([(k, False, False) for k in key_cols])
         try:
             nc = self.num_cols
             kc = (C.c_int32 * len(key_cols))(*key_cols)
             arr = (A.GroupOut * len(spec))()
             for j, (kind, t) in enumerate(spec):
-                is_fp, nullable, null_bits = self._column_null(t) if t >= 0 else (False, False, 0)
+                is_fp, nullable, null_bits = self._column_null(t)
                 arr[j] = A.GroupOut(t, GROUP_KINDS[kind], int(is_fp), int(nullable), 0, A.to_i64(null_bits))
 
             def call(out_ptr, capacity, row_count_ptr):
@@ -336,35 +363,30 @@ class DeviceColumns:
         partition keys ascending with NULLs last, then by `order_by` (hdk_hip_sort_columns, stable), straight into the
         first columns of the one block that also holds the window columns, which the library writes.  More outs than one
         call takes go through further calls over the same sorted columns."""
-        part_cols, order, spec, descs = resolve_window_columns(self.columns(), partition_by, order_by, outs)
+        part_cols, order, spec, descs = resolve_window_columns(self.schema, partition_by, order_by, outs)
         nc, nw, n = self.num_cols, len(spec), self.num_rows
-        out = DeviceColumns(self.compiled, self.mgr, self.device_id, None, 0, 0, self.error_code, self.columns() + descs)
+        out = self._like(None, 0, 0, self.schema + descs)
         if n == 0:
             return out
-        if self.block is None or not self.block.ptr:
-            raise ValueError("the columns have been freed")
+        src = self._block_ptr()
         entries = [] if presorted else [(k, False, False) for k in part_cols] + order
         if len(entries) > A.MAX_ORDER_ENTRIES:
             raise QueryMustRunOnCpu("more than %d partition keys and order entries to sort by" % A.MAX_ORDER_ENTRIES)
         block = self.mgr.alloc((nc + nw) * n * 8, self.device_id)
         try:
             if not entries:
-                for t in range(nc):
-                    self.mgr.copyDeviceToDevice(block.ptr + t * n * 8, self.device_ptr(t), n * 8, self.device_id, self.device_id)
+                self._copy_rows(block, 0, n)
             else:
-                arr = (A.OrderEntry * len(entries))()
-                for i, (t, desc, nulls_first) in enumerate(entries):
-                    is_fp, nullable, null_bits = self._column_null(t)
-                    arr[i] = A.OrderEntry(t, int(desc), int(nulls_first), int(is_fp), int(nullable), A.to_i64(null_bits))
-                check(lib().hdk_hip_sort_columns(self.block.ptr, self.capacity, nc, n, arr, len(entries), 0, 0, 0, block.ptr, n,
-                                                 None, None, 0, self.device_id, None))
+                arr = self._order_entries(entries)
+                check(lib().hdk_hip_sort_columns(src, self.capacity, nc, n, arr, len(entries), 0, 0, 0, block.ptr, n, None, None,
+                                                 0, self.device_id, None))
             pc = (C.c_int32 * max(len(part_cols), 1))(*part_cols)
             oc = (C.c_int32 * max(len(order), 1))(*[t for t, _, _ in order])
             for j0 in range(0, nw, A.MAX_WINDOW_OUTS):
                 part = spec[j0:j0 + A.MAX_WINDOW_OUTS]
                 warr = (A.WindowOut * len(part))()
                 for j, w in enumerate(part):
-                    is_fp, nullable, null_bits = self._column_null(w.col) if w.col >= 0 else (False, False, 0)
+                    is_fp, nullable, null_bits = self._column_null(w.col)
                     warr[j] = A.WindowOut(w.col, w.kind, w.frame, int(is_fp), int(nullable), A.to_i64(null_bits), w.param)
                 check(lib().hdk_hip_window_columns(block.ptr, n, nc, n, pc, len(part_cols), oc, len(order), warr, len(part),
                                                    block.ptr + (nc + j0) * n * 8, n, None, 0, self.device_id, None))
@@ -384,12 +406,7 @@ class DeviceColumns:
             return self.sort([])  # nothing to add: every row, copied
         cols = self
         for partition_by, order_by, idx in group_windows(windows):
-            try:
-                nxt = cols.window(partition_by, order_by, [windows[i] for i in idx])
-            finally:
-                if cols is not self:
-                    cols.free()
-            cols = nxt
+            cols = _stage(cols, lambda c: c.window(partition_by, order_by, [windows[i] for i in idx]), keep=self)
         return cols
 
     def project(self, outs) -> "DeviceColumns":
@@ -401,13 +418,12 @@ class DeviceColumns:
         beyond one call's outs, ops or input columns goes through further calls that write into the same block.  One
         stream synchronisation, after which the error word is read: a division by zero or an overflow that a row raised
         frees the block and raises HdkHipError with the reference's code."""
-        programs, descs = resolve_select_columns(self.columns(), outs)
-        out = DeviceColumns(self.compiled, self.mgr, self.device_id, None, 0, 0, self.error_code, descs)
+        programs, descs = resolve_select_columns(self.schema, outs)
+        out = self._like(None, 0, 0, descs)
         n = self.num_rows
         if n == 0:
             return out
-        if self.block is None or not self.block.ptr:
-            raise ValueError("the columns have been freed")
+        src = self._block_ptr()
         calls = split_project_calls(programs)
         block = self.mgr.alloc(len(programs) * n * 8, self.device_id)
         try:
@@ -424,14 +440,14 @@ class DeviceColumns:
                         for code, width, flags, col, imm in p.ops:
                             ops[at] = A.ProjectOp(code, width, flags, 0, col, A.to_i64(imm))
                             at += 1
-                    check(lib().hdk_hip_project_columns(self.block.ptr, self.capacity, self.num_cols, n, ops, at, parr, count,
+                    check(lib().hdk_hip_project_columns(src, self.capacity, self.num_cols, n, ops, at, parr, count,
                                                         block.ptr + j0 * n * 8, n, errors.ptr + 4 * c, self.device_id, None))
                 self.mgr.synchronizeStream(self.device_id)
                 err = int(self.mgr.to_host(errors.ptr, 4 * len(calls), self.device_id, np.int32).max())
             finally:
                 errors.free()
             if err:
-                raise HdkHipError(err, f"device error code {err} (QE/Execute.h:1019-1031)")
+                raise _device_error(err)
         except Exception:
             block.free()
             raise
@@ -683,12 +699,17 @@ class PreparedStep:
             self.init_output(stream)
             self.launch(stream)
 
-    def fetch(self, stream_synced=False) -> ExecutionResult:
+    def _error_code(self, stream_synced: bool) -> int:
+        """The step's error word once the stream has drained; a positive code raises."""
         if not stream_synced:
             self.mgr.synchronizeStream(self.dev)
         err = int(self.mgr.to_host(self.d_err.ptr, 4, self.dev, np.int32)[0])
         if err > 0:
-            raise HdkHipError(err, f"device error code {err} (QE/Execute.h:1019-1031)")
+            raise _device_error(err)
+        return err
+
+    def fetch(self, stream_synced=False) -> ExecutionResult:
+        err = self._error_code(stream_synced)
         buf = self.mgr.to_host(self.out_ptr, max(self.buffer_bytes, 8), self.dev, np.int64)
         total = None
         if self.cp.plan.query_kind == A.Q_PROJECTION:
@@ -707,11 +728,7 @@ class PreparedStep:
         of entry_count rows per column -- over-allocating a few MB costs less than a second pass over the table.  Above
         that the groups are counted first (out_cols = NULL: one streaming pass) and the block holds exactly row_count
         rows per column: a half-empty 200 M-entry table then takes 1.6 GB, not 3.2 GB."""
-        if not stream_synced:
-            self.mgr.synchronizeStream(self.dev)
-        err = int(self.mgr.to_host(self.d_err.ptr, 4, self.dev, np.int32)[0])
-        if err > 0:
-            raise HdkHipError(err, f"device error code {err} (QE/Execute.h:1019-1031)")
+        err = self._error_code(stream_synced)
         p = self.cp.plan
         n, nt = int(self.cp.entry_count), int(p.num_targets)
         iv = np.ascontiguousarray(self.cp.init_vals, dtype=np.int64)
@@ -937,31 +954,8 @@ class Executor:
             try:
                 if result == "columns":
                     step.enqueue()
-                    cols = step.fetch_columns()
-                    if step.cp.having is not None:  # HAVING, then the query's SortInfo, applied where the columns are;
-                        try:                        # every intermediate block is handed back
-                            kept = cols.filter(step.cp.having)
-                        finally:
-                            cols.free()
-                        cols = kept
-                    if sq.windows:  # after HAVING and before the SortInfo, which may name a window column
-                        try:
-                            windowed = cols.windows(sq.windows)
-                        finally:
-                            cols.free()
-                        cols = windowed
-                    if sq.select:  # after the windows, whose columns it may read; the SortInfo names ITS columns
-                        try:
-                            projected = cols.project(sq.select)
-                        finally:
-                            cols.free()
-                        cols = projected
-                    if not sorts:
-                        return cols
-                    try:
-                        return cols.sort(sq.order_by if sq.windows or sq.select else step.cp.order_by, sq.limit, sq.offset)
-                    finally:
-                        cols.free()
+                    return run_stages(step.fetch_columns(), step.cp.having, sq.windows, sq.select, sq.order_by, sq.limit,
+                                      sq.offset)
                 return step.run()
             except HdkHipError as e:
                 if e.code != A.ERR_OUT_OF_SLOTS or step.cp.plan.query_kind != A.Q_BASELINE_HASH or retries_left == 0:
@@ -978,31 +972,5 @@ class Executor:
         HAVING and the SortInfo apply to the regrouped columns.  Every intermediate block is handed back."""
         inner, rg = split_count_distinct(q)
         cols = self.execute(inner, frag_ids=frag_ids, result="columns", **kw)
-        try:
-            out = cols.group_by(rg.keys, rg.outs)
-        finally:
-            cols.free()
-        if rg.having:
-            try:
-                kept = out.filter(rg.having)
-            finally:
-                out.free()
-            out = kept
-        if rg.windows:
-            try:
-                windowed = out.windows(rg.windows)
-            finally:
-                out.free()
-            out = windowed
-        if rg.select:
-            try:
-                projected = out.project(rg.select)
-            finally:
-                out.free()
-            out = projected
-        if not (rg.order_by or rg.limit is not None or rg.offset):
-            return out
-        try:
-            return out.sort(rg.order_by, rg.limit, rg.offset)
-        finally:
-            out.free()
+        out = _stage(cols, lambda c: c.group_by(rg.keys, rg.outs))
+        return run_stages(out, rg.having, rg.windows, rg.select, rg.order_by, rg.limit, rg.offset)

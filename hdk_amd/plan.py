@@ -326,11 +326,11 @@ class OutCol:
 
 @dataclass(frozen=True)
 class ColumnDesc:
-    """One dense device column described by itself: what a DeviceColumns that no longer has the schema of a CompiledPlan
-    (DeviceColumns.group_by) carries per column.  is_fp / nullable / null_bits say how the 8-byte words compare and which
-    word is the in-band NULL (hdk_hip_order_entry's fields); type, dictionary and scale say how to_columns() / to_arrow()
-    present them (a string id through its dictionary, a scaled decimal divided by 10 ** scale).  Reads like an OutCol
-    where one is expected (resolve_order_by, resolve_having_columns)."""
+    """One dense device column described by itself: what every DeviceColumns carries per column (describe_columns for a
+    plan's result, then what group_by / window / project make of it).  is_fp / nullable / null_bits say how the 8-byte
+    words compare and which word is the in-band NULL (hdk_hip_order_entry's fields); type, dictionary and scale say how
+    to_columns() / to_arrow() present them (a string id through its dictionary, a scaled decimal divided by 10 ** scale).
+    Reads like an OutCol where one is expected (resolve_order_by)."""
     name: str
     is_fp: bool
     nullable: bool
@@ -1215,43 +1215,42 @@ _MIRROR = {A.CMP_EQ: A.CMP_EQ, A.CMP_NE: A.CMP_NE, A.CMP_LT: A.CMP_GT, A.CMP_GT:
 
 def resolve_having(cp: CompiledPlan, having) -> Optional[Having]:
     """HAVING conditions (a conjunction of Cmp / And / Or / Not trees over TargetRef and Lit) -> Having, against the dense
-    columns of `cp`.  Per side is_fp / nullable / null_bits are result_set.dense_column_null's; the comparison is made in
-    doubles when either side is fp or the literal is a float.  An unknown target name or index is a ValueError; what the
-    library's call cannot express (a dictionary-encoded or decimal target, arithmetic inside a leaf, more than
-    MAX_HAVING_LEAVES comparisons, a program beyond MAX_FILTER_OPS) must run on the CPU."""
-    from .result_set import dense_column_null
+    columns of `cp` (describe_columns).  A step that is not a group-by has none and must run on the CPU."""
     having = list(having)
     if not having:
         return None
     kind = cp.plan.query_kind
     if kind != A.Q_PERFECT_HASH and kind != A.Q_BASELINE_HASH:
         raise QueryMustRunOnCpu("HAVING on a step that is not a group-by: it has no dense device columns")
-    return resolve_having_columns(cp.out_cols, int(cp.plan.num_targets), lambda t: dense_column_null(cp, t), having)
+    return resolve_having_columns(describe_columns(cp), having)
 
 
-def resolve_having_columns(out_cols, nt: int, null_of, having) -> Optional[Having]:
-    """resolve_having against any dense columns: `out_cols` describe them the way OutCol does (name, target_idx, type,
-    dictionary, scale -- a ColumnDesc will do) and null_of(t) gives column t's (is_fp, nullable, null_bits)."""
+def resolve_having_columns(cols: List[ColumnDesc], having) -> Optional[Having]:
+    """HAVING conditions against the dense columns `cols`.  Per side is_fp / nullable / null_bits are the ColumnDesc's; the
+    comparison is made in doubles when either side is fp or the literal is a float.  An unknown target name or index is a
+    ValueError; what the library's call cannot express (a dictionary-encoded or decimal target, arithmetic inside a leaf,
+    more than MAX_HAVING_LEAVES comparisons, a program beyond MAX_FILTER_OPS) must run on the CPU."""
     having = list(having)
     if not having:
         return None
-    by_name = {oc.name: oc for oc in out_cols}
-    by_idx = {oc.target_idx: oc for oc in out_cols}
+    nt = len(cols)
+    by_name = {d.name: d for d in cols}
+    by_idx = {d.target_idx: d for d in cols}
 
-    def target(e: TargetRef) -> int:
+    def target(e: TargetRef) -> ColumnDesc:
         if isinstance(e.target, str):
             if e.target not in by_name:
                 raise ValueError(f"HAVING names no target: {e.target!r}")
-            oc = by_name[e.target]
+            d = by_name[e.target]
         else:
             if isinstance(e.target, bool) or not 0 <= int(e.target) < nt:
                 raise ValueError(f"HAVING target index {e.target!r} outside 0..{nt - 1}")
-            oc = by_idx[int(e.target)]
-        if oc.dictionary is not None or oc.type.kind == "dict":
-            raise QueryMustRunOnCpu(f"HAVING on a dictionary-encoded target ({oc.name}): the dense column holds string ids")
-        if oc.type.kind == "decimal" or oc.scale:
-            raise QueryMustRunOnCpu(f"HAVING on a decimal target ({oc.name}): the dense column holds scaled values")
-        return oc.target_idx
+            d = by_idx[int(e.target)]
+        if d.dictionary is not None or d.type.kind == "dict":
+            raise QueryMustRunOnCpu(f"HAVING on a dictionary-encoded target ({d.name}): the dense column holds string ids")
+        if d.type.kind == "decimal" or d.scale:
+            raise QueryMustRunOnCpu(f"HAVING on a decimal target ({d.name}): the dense column holds scaled values")
+        return d
 
     def leaf(c: Cmp) -> HavingLeaf:
         if c.op not in _CMP:
@@ -1262,13 +1261,12 @@ def resolve_having_columns(out_cols, nt: int, null_of, having) -> Optional[Havin
         if not isinstance(lhs, TargetRef) or not isinstance(rhs, (TargetRef, Lit)):
             raise QueryMustRunOnCpu(f"HAVING compares a target with a literal or a target; arithmetic inside a comparison "
                                     f"({c!r}) is outside the fixed kernel library")
-        lt = target(lhs)
-        l_fp, l_nullable, l_null = null_of(lt)
+        d = target(lhs)
+        lt, l_fp, l_nullable, l_null = d.target_idx, d.is_fp, d.nullable, d.null_bits
         if isinstance(rhs, TargetRef):
-            rt = target(rhs)
-            r_fp, r_nullable, r_null = null_of(rt)
-            return HavingLeaf(lt, cmp, True, rt, 0, bool(l_fp or r_fp), bool(l_fp), bool(l_nullable), A.to_i64(l_null),
-                              bool(r_fp), bool(r_nullable), A.to_i64(r_null))
+            r = target(rhs)
+            return HavingLeaf(lt, cmp, True, r.target_idx, 0, bool(l_fp or r.is_fp), bool(l_fp), bool(l_nullable),
+                              A.to_i64(l_null), bool(r.is_fp), bool(r.nullable), A.to_i64(r.null_bits))
         v = rhs.value
         if isinstance(v, (bool, np.bool_)):
             v = int(v)

@@ -12,7 +12,7 @@ from typing import Dict, List
 import numpy as np
 
 from . import _abi as A
-from .plan import CompiledPlan, align8, columnar_slot_offsets
+from .plan import CompiledPlan, align8, columnar_slot_offsets, describe_columns
 
 
 def _slot_arrays(cp: CompiledPlan, buf: np.ndarray, entry_count: int) -> List[np.ndarray]:
@@ -158,12 +158,10 @@ def to_columns(cp: CompiledPlan, buf: np.ndarray, entry_count=None, nrows=None) 
     return res
 
 
-def _column_values(cp: CompiledPlan, oc, vals: np.ndarray, cnt, w: int, dense: bool = False) -> list:
-    """One output column as a python list (None = NULL) from the values of its non-empty entries, in entry order.
-    dense=False: `vals` are the slot (or key) words sign-extended to int64 and `cnt` AVG's count slot -- what the host
-    reader takes out of a buffer.  dense=True: `vals` are the 8-byte values of a device column
-    (hdk_hip_columnarize_result): a float accumulator is already widened to double bits (NULL_FLOAT -> NULL_DOUBLE for a
-    nullable argument) and AVG is already divided (NULL_DOUBLE for count 0); `cnt` is None.  `w`: the slot's width in the buffer."""
+def _column_values(cp: CompiledPlan, oc, vals: np.ndarray, cnt, w: int) -> list:
+    """One output column as a python list (None = NULL) from the values of its non-empty entries, in entry order: `vals`
+    are the slot (or key) words sign-extended to int64 and `cnt` AVG's count slot -- what the host reader takes out of a
+    buffer.  `w`: the slot's width in the buffer."""
     p = cp.plan
     tg = p.targets[oc.target_idx]
     if oc.kind == "key":
@@ -194,16 +192,6 @@ def _column_values(cp: CompiledPlan, oc, vals: np.ndarray, cnt, w: int, dense: b
         nullv = int(np.int64(nullv).astype(np.int32))
     nullable = bool(tg.skip_null)
     float_slot = tg.arg_is_fp == A.FP_SLOT_FLOAT
-    if dense and (float_slot or oc.agg == "avg"):
-        # the device has done the widening / the division; its NULL is NULL_DOUBLE (a nullable float accumulator, AVG's
-        # count 0).  (An AVG that comes out as exactly DBL_MIN would read as NULL here: sums of that size do not occur.)
-        bits = np.ascontiguousarray(vals, dtype=np.int64)
-        can_be_null = oc.agg == "avg" or nullable
-        col = [None if (can_be_null and b == A.NULL_DOUBLE_BITS) else f
-               for b, f in zip(bits.tolist(), bits.view(np.float64).tolist())]
-        if oc.scale and oc.agg in ("sum", "min", "max", "avg"):
-            col = [None if v is None else v / 10 ** oc.scale for v in col]
-        return col
     if float_slot:
         # takes_float_argument: the value is the float in the slot's low 4 bytes (ResultSetIteration.cpp:50-60,
         # actual_compact_sz = sizeof(float)); NULL when those bits are the float sentinel
@@ -242,7 +230,9 @@ def _column_values(cp: CompiledPlan, oc, vals: np.ndarray, cnt, w: int, dense: b
 
 def dense_column_null(cp: CompiledPlan, target_idx: int):
     """(is_fp, nullable, null_bits) of target `target_idx`'s dense device column: how its 8-byte words compare (as doubles or
-    as int64) and which word, if any, is its in-band NULL -- by the rules _column_values(dense=True) reads the column with."""
+    as int64) and which word, if any, is its in-band NULL, as hdk_hip_columnarize_result writes it: a float accumulator widened
+    to double bits (NULL_FLOAT -> NULL_DOUBLE for a nullable argument), AVG divided (NULL_DOUBLE for count 0; an AVG that
+    comes out as exactly DBL_MIN would read as NULL: sums of that size do not occur).  plan.describe_columns restates it."""
     tg = cp.plan.targets[target_idx]
     if tg.agg == A.AGG_ID:
         kt = cp.key_types[tg.key_idx]
@@ -264,13 +254,7 @@ def dense_to_columns(cp: CompiledPlan, dense: List[np.ndarray]) -> Dict[str, lis
     """to_columns() from dense device columns: dense[t] holds target t's 8-byte values (int64 words), one per group in
     entry order, as hdk_hip_columnarize_result writes them.  The same names, order, NULLs, dictionary strings and
     decimal scaling as to_columns() on the buffer the columns were made from."""
-    first_slot, s = [], 0
-    for ti in range(cp.plan.num_targets):
-        first_slot.append(s)
-        s += 2 if cp.plan.targets[ti].agg == A.AGG_AVG else 1
-    return {oc.name: _column_values(cp, oc, np.ascontiguousarray(dense[oc.target_idx]).view(np.int64), None,
-                                    cp.slot_widths[first_slot[oc.target_idx]], dense=True)
-            for oc in cp.out_cols}
+    return described_to_columns(describe_columns(cp), dense)
 
 
 def to_arrow(cp: CompiledPlan, buf: np.ndarray, entry_count=None, nrows=None):
@@ -298,7 +282,7 @@ def columns_to_arrow(cp: CompiledPlan, cols: Dict[str, list]):
 
 
 def described_to_columns(schema, dense: List[np.ndarray]) -> Dict[str, list]:
-    """to_columns() for dense columns that describe themselves (plan.ColumnDesc; DeviceColumns.group_by): dense[t] holds
+    """to_columns() for dense columns by their description (plan.ColumnDesc; DeviceColumns.schema): dense[t] holds
     column t's int64 words.  None for a NULL word, a dictionary's string for a string id, a double for an fp column, a
     scaled decimal divided by 10 ** scale."""
     res = {}
@@ -328,7 +312,9 @@ def described_to_arrow(schema, cols: Dict[str, list]):
             ty = pa.string()
         elif d.is_fp or (d.scale and d.agg != "count"):
             ty = pa.float64()
-        elif d.agg in ("count", "sum"):
+        elif d.agg == "count":
+            ty = pa.int32() if d.type.size == 4 else pa.int64()
+        elif d.agg == "sum":
             ty = pa.int64()
         else:
             ty = {1: pa.int8(), 2: pa.int16(), 4: pa.int32(), 8: pa.int64()}.get(d.type.size, pa.int64())

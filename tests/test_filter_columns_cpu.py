@@ -275,6 +275,9 @@ def test_decimal_targets_are_rejected():
                   having=[Cmp(TargetRef("s"), ">", Lit(2))])
     with pytest.raises(QueryMustRunOnCpu, match="decimal"):
         compile_query(st, q)
+    # COUNT of a decimal is a plain count: its column has no scale (describe_columns), as after a regroup
+    counted = dataclasses.replace(q, targets=[KeyRef(0, "k"), Agg("count", ColRef("d"), "n")], having=[Cmp(TargetRef("n"), ">", Lit(1))])
+    assert compile_query(st, counted).having.leaves[0].lhs_col == 1
 
 
 def test_buffer_result_with_having_is_an_error():
@@ -285,3 +288,47 @@ def test_buffer_result_with_having_is_an_error():
         ex.execute(q, result="buffer")
     with pytest.raises(ValueError, match="columns"):
         ex.execute(q)
+
+
+# (leaves as HavingLeaf's fields in order, program), written down from the resolver as it was when it read OutCols and
+# result_set.dense_column_null: an fp target (fm, a), nullable ones (k32, m, a, s), a target on the right, a literal on the left
+_RESOLVED = {
+    "baseline_having_then_order_by_key": ([(0, 6, False, 0, 0, False, False, True, -2147483648, False, False, 0),
+                                           (1, 6, False, 0, 15, False, False, False, 0, False, False, 0)], [0, 1, 64]),
+    "baseline_nullable_k32_key_and_max": ([(0, 6, False, 0, 0, False, False, True, -2147483648, False, False, 0),
+                                           (2, 4, False, 0, 10, False, False, True, -9223372036854775808, False, False, 0)], []),
+    "everything_passes": ([(1, 6, False, 0, 1, False, False, False, 0, False, False, 0)], []),
+    "float_min_against_a_float_literal": ([(1, 3, False, 0, -4598456694521987072, True, True, True, 4503599627370496, True, False, 0)], []),
+    "having_order_limit_offset": ([(1, 4, False, 0, 18, False, False, False, 0, False, False, 0),
+                                   (3, 3, False, 0, 4617315517961601024, True, True, True, 4503599627370496, True, False, 0)], []),
+    "literal_on_the_left_or_not": ([(1, 4, False, 0, 25, False, False, False, 0, False, False, 0),
+                                    (3, 6, False, 0, 0, True, True, True, 4503599627370496, True, False, 0),
+                                    (0, 2, False, 0, 7, False, False, True, -9223372036854775808, False, False, 0)], [0, 1, 66, 65, 2, 64]),
+    "nothing_passes": ([(1, 4, False, 0, 1000000, False, False, False, 0, False, False, 0)], []),
+    "perfect_count_and_nullable_avg": ([(1, 4, False, 0, 18, False, False, False, 0, False, False, 0),
+                                        (3, 3, False, 0, 4617315517961601024, True, True, True, 4503599627370496, True, False, 0)], []),
+    "target_against_target": ([(2, 4, True, 1, 0, False, False, True, -9223372036854775808, False, False, 0)], []),
+}
+
+
+def test_resolve_having_gives_what_it_gave_from_out_cols():
+    """resolve_having over describe_columns(cp) resolves the GPU suite's HAVINGs leaf for leaf and program for program as
+    it did over cp.out_cols, and each leaf is the one having_expect builds from the column's (is_fp, nullable, null_bits)."""
+    import test_gpu_having_queries as G
+    from hdk_amd import result_set as rs
+    from hdk_amd.plan import describe_columns, resolve_having, resolve_having_columns
+    st = G._storage()
+    assert sorted(G._QUERIES) == sorted(_RESOLVED)
+    for name, q in G._QUERIES.items():
+        cp = compile_query(st, q)
+        hv = resolve_having(cp, q.having)
+        assert ([dataclasses.astuple(lf) for lf in hv.leaves], hv.prog) == _RESOLVED[name], name
+        assert hv == cp.having == resolve_having_columns(describe_columns(cp), q.having), name
+        for lf in hv.leaves:
+            info = rs.dense_column_null(cp, lf.lhs_col)
+            if lf.rhs_is_col:
+                want = H.col_leaf(lf.lhs_col, lf.cmp, lf.rhs_col, info, rs.dense_column_null(cp, lf.rhs_col))
+            else:
+                lit = float(np.int64(lf.rhs_lit).view(np.float64)) if lf.rhs_is_fp else lf.rhs_lit
+                want = H.lit_leaf(lf.lhs_col, lf.cmp, lit, info)
+            assert dataclasses.astuple(lf) == tuple(want), (name, lf)

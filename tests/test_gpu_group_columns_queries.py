@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from hdk_amd import _abi as A
-from hdk_amd.ir import Agg, Cmp, ColRef, KeyRef, Lit, OrderEntry, QueryMustRunOnCpu, QueryUnit, TargetRef
-from hdk_amd.plan import compile_query
+from hdk_amd.ir import Agg, Cmp, ColRef, KeyRef, Lit, OrderEntry, Proj, QueryMustRunOnCpu, QueryUnit, TargetRef
+from hdk_amd.plan import compile_query, describe_columns
 from hdk_amd.storage import ArrowStorage
 
 pytestmark = pytest.mark.gpu
@@ -92,7 +92,7 @@ def test_roll_up_equals_the_direct_group_by(gpu_executor_factory, storage, table
     cols = ex.execute(fine, result="columns")
     want = ex.execute(direct, result="columns")
     try:
-        assert cols.schema is None and cols.num_rows > 5 * want.num_rows
+        assert cols.columns() == describe_columns(cols.compiled) and cols.num_rows > 5 * want.num_rows
         rolled = cols.group_by(["k"], _ROLLUP)
         try:
             assert rolled.num_rows == want.num_rows == 300 and rolled.schema is not None
@@ -201,11 +201,19 @@ def test_a_regrouped_result_carries_its_schema(gpu_executor_factory, table):
                            Agg("max", ColRef("v"), "mx")])
     cols = ex.execute(q, result="columns")
     try:
-        # a plan-made result behaves as before: no schema of its own, the plan's readers
-        assert cols.schema is None and cols.num_cols == 5
+        # a plan-made result's schema is the plan's description, and it reads as the buffer does
+        assert cols.columns() == describe_columns(cols.compiled) and cols.num_cols == 5
         plain = ex.execute(q)
         assert sorted(zip(*cols.to_columns().values())) == sorted(zip(*plain.to_columns().values()))
         assert cols.to_arrow().schema == plain.to_arrow().schema
+        # ... whether or not a stage ran first: a pass-through select keeps every type, the 4-byte COUNT's included
+        picked = ex.execute(dataclasses.replace(q, select=[Proj(TargetRef(c), c) for c in ("s", "k", "n", "sf", "mx")]),
+                            result="columns")
+        try:
+            assert picked.to_arrow().schema == cols.to_arrow().schema
+            assert str(picked.to_arrow().schema.field("n").type) == "int32"
+        finally:
+            picked.free()
         by_s = cols.group_by(["s"], [("id", "s", None), ("sum", "n", "rows"), ("max", "mx", None), ("sum", "sf", "total"),
                                      ("count", None, "keys"), ("max", "s", "last")])
         try:

@@ -268,8 +268,7 @@ def test_regroup_resolves_keys_outs_types_and_names():
     assert resolve_order_by(out, len(out), [OrderEntry("rows", True), OrderEntry(3)]) == [(1, True, False), (3, False, False)]
     with pytest.raises(QueryMustRunOnCpu):
         resolve_order_by(out, len(out), [OrderEntry("last_s")])
-    hv = resolve_having_columns(out, len(out), lambda t: (out[t].is_fp, out[t].nullable, out[t].null_bits),
-                                [Cmp(TargetRef("rows"), ">", Lit(3)), Cmp(TargetRef("mf"), "<", Lit(2.5))])
+    hv = resolve_having_columns(out, [Cmp(TargetRef("rows"), ">", Lit(3)), Cmp(TargetRef("mf"), "<", Lit(2.5))])
     assert [(lf.lhs_col, lf.cmp_fp, lf.lhs_nullable) for lf in hv.leaves] == [(1, False, False), (3, True, True)]
 
 
