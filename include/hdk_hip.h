@@ -498,7 +498,18 @@ int32_t hdk_hip_workspace_size(const hdk_hip_plan* plan, const hdk_hip_kernel_op
  * value, MIN / MAX combine with it, a slot that still holds its NULL sentinel takes the launch's first value, a new group is
  * claimed where the reference's probe sequence finds it.  Launches over disjoint row sets into one buffer therefore equal
  * one launch over all the rows (tests/test_gpu_relaunch.py, every aggregate route).  HDK_HIP_LAUNCH_INIT_OUTPUT is the one
- * exception: it overwrites the buffer with the empty image first. */
+ * exception: it overwrites the buffer with the empty image first.
+ * Error codes (ERROR_CODE[0], an int32 the caller zeroes before the launch): a row raises HDK_HIP_ERR_DIV_BY_ZERO (integer / and
+ * %, floating-point / by 0.0 or -0.0) or HDK_HIP_ERR_OVERFLOW_OR_UNDERFLOW (a checked + - * whose exact result leaves the
+ * step's SQL type of check_width bytes) only if the reference's row function evaluates the step for it: the row passes the
+ * filters, has a partner in every INNER join, and neither operand is NULL (an inner column of a LEFT join without a partner
+ * reads as NULL).  A result equal to the smallest or the largest value of the type raises nothing.  When several codes are
+ * raised in one launch -- by different rows, or together with OUT_OF_SLOTS, OUT_OF_TIME or INTERRUPTED -- the word holds the
+ * numerically LARGEST positive code (every kernel records with an atomic maximum; the reference keeps the first code a thread
+ * happens to store, which is no more specified).  After a positive code the contents of the output buffer are unspecified:
+ * later passes of a multi-pass route and an armed fallback kernel may or may not have run.  The launch leaves nothing else
+ * behind: the next launch with the same workspace, plan and parameters is not affected by it
+ * (tests/test_gpu_error_cases.py, every route that evaluates an arithmetic step). */
 int32_t hdk_hip_launch(const hdk_hip_plan* plan, int8_t* const params[HDK_KP_COUNT],
                        const hdk_hip_kernel_options* ko, int32_t device_id, void* stream,
                        void* workspace, size_t workspace_bytes);

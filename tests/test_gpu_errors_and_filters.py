@@ -179,14 +179,28 @@ def test_filter_program_deeper_than_the_streaming_stack(oracle, gpu_executor_fac
 
 
 def _expect_error(oracle, gpu_executor_factory, st, q, code):
+    """-> the first kernel each strategy ran"""
     cp, want, err = run_oracle(oracle, st, q)
     assert err == code, err
+    first = {}
     for flags in STRATEGIES:
         if flags == A.LAUNCH_FORCE_GLOBAL_ATOMICS and cp.plan.query_kind == A.Q_NON_GROUPED:
             continue
-        with pytest.raises(HdkHipError) as ei:
-            gpu_executor_factory(st).execute(cp, flags=flags)
+        step = gpu_executor_factory(st).prepare(cp, flags=flags)
+        try:
+            first[flags] = step.kernel_names().split(",")[0]
+            with pytest.raises(HdkHipError) as ei:
+                step.run()
+        finally:
+            step.free()
         assert ei.value.code == code, (flags, ei.value.code)
+    # the strategies are different kernels: a routing change cannot quietly turn them into one.  (FORCE_GENERIC names the
+    # batched interpreter, which is also what the plain launch of these expression plans runs unless a specialised kernel takes it.)
+    assert first[A.LAUNCH_FORCE_GENERIC] == "hdk_scan_agg_vec" and first[A.LAUNCH_FORCE_SCALAR] == "hdk_scan_agg_generic", first
+    assert first[0] in ("hdk_scan_agg_vec", "hdk_scan_agg_direct"), first
+    if A.LAUNCH_FORCE_GLOBAL_ATOMICS in first:
+        assert first[A.LAUNCH_FORCE_GLOBAL_ATOMICS] == "hdk_scan_agg_global", first
+    return first
 
 
 def test_division_by_zero_is_reported(oracle, gpu_executor_factory):
@@ -194,7 +208,8 @@ def test_division_by_zero_is_reported(oracle, gpu_executor_factory):
     for q in (QueryUnit("t", groupby=[ColRef("k")], targets=[KeyRef(0), Agg("sum", ColRef("b") / ColRef("a"))]),
               QueryUnit("t", quals=[Cmp(ColRef("b") % ColRef("a"), "=", Lit(1))], targets=[Agg("count")]),
               QueryUnit("t", targets=[Agg("sum", ColRef("d") / ColRef("a"))])):
-        _expect_error(oracle, gpu_executor_factory, st, q, A.ERR_DIV_BY_ZERO)
+        seen = set(_expect_error(oracle, gpu_executor_factory, st, q, A.ERR_DIV_BY_ZERO).values())
+        assert seen >= {"hdk_scan_agg_vec", "hdk_scan_agg_generic"} and len(seen) == (3 if q.groupby else 2), seen
 
 
 def test_integer_overflow_is_reported(oracle, gpu_executor_factory):
@@ -216,8 +231,10 @@ def test_integer_overflow_is_reported(oracle, gpu_executor_factory):
            QueryUnit("t", targets=[Agg("max", ColRef("x64") * ColRef("x64"))]),
            QueryUnit("t", quals=[Cmp(ColRef("x32") + Lit(2_147_480_000), ">", Lit(0))], targets=[Agg("count")]),
            QueryUnit("t", groupby=[ColRef("k")], targets=[KeyRef(0), Agg("min", ColRef("x64") * Lit(2**30))])]
+    seen = set()
     for q in bad:
-        _expect_error(oracle, gpu_executor_factory, st, q, A.ERR_OVERFLOW_OR_UNDERFLOW)
+        seen |= set(_expect_error(oracle, gpu_executor_factory, st, q, A.ERR_OVERFLOW_OR_UNDERFLOW).values())
+    assert seen == {"hdk_scan_agg_vec", "hdk_scan_agg_generic", "hdk_scan_agg_global", "hdk_scan_agg_direct"}, seen
     good = [QueryUnit("t", groupby=[ColRef("k")], targets=[KeyRef(0), Agg("sum", ColRef("small") * ColRef("small"))]),
             QueryUnit("t", groupby=[ColRef("k")], targets=[KeyRef(0), Agg("sum", ColRef("x32") * ColRef("y32n")),
                                                           Agg("count", ColRef("x32") * ColRef("y32n"))]),
