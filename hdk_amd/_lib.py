@@ -73,6 +73,7 @@ SIGNATURES = {
     "hdk_hip_partition_baseline": (i32, [C.POINTER(A.Plan), v, u32, v, i32, C.POINTER(u32), C.POINTER(v), i32, v]),
     "hdk_hip_result_columns_workspace_bytes": (sz, [u32]),
     "hdk_hip_columnarize_result": (i32, [C.POINTER(A.Plan), v, u32, v, v, C.c_uint64, v, v, sz, i32, v]),
+    "hdk_hip_columnarize_rows": (i32, [C.POINTER(A.Plan), v, u32, v, v, C.c_uint64, v, v, i32, v]),
     "hdk_hip_sort_columns_workspace_bytes": (sz, [C.c_uint64, i32]),
     "hdk_hip_sort_columns": (i32, [v, C.c_uint64, i32, C.c_uint64, C.POINTER(A.OrderEntry), i32, C.c_uint64, C.c_uint64, u32,
                                    v, C.c_uint64, v, v, sz, i32, v]),

@@ -20,6 +20,7 @@
 #include "column_primitives.h"
 #include "group_buffer.h"
 #include "host_common.h"
+#include "result_value.h"
 
 namespace hdk {
 
@@ -30,15 +31,6 @@ constexpr int kRcWaves = kRcBlock / kWave;
 constexpr int kRcParts = kRcItems * kRcWaves;  // (item, wave) partial counts of a tile, in entry order
 static_assert(kRcParts == kWave, "one wave scans the partial counts of a tile");
 constexpr ScanPer kRcScanPer = SCAN_PER_4;  // tile counts per thread and trip of the scan
-
-enum RcOp : uint32_t {
-  RC_COPY = 0,            // the slot (or key), sign-extended; doubles keep their bits
-  RC_FLOAT = 1,           // float in the low 4 bytes -> double
-  RC_FLOAT_NULLABLE = 2,  // ... and NULL_FLOAT -> NULL_DOUBLE
-  RC_AVG_INT = 3,         // pair_to_double: (double)sum / (double)count, NULL_DOUBLE for count 0
-  RC_AVG_DOUBLE = 4,
-  RC_AVG_FLOAT = 5
-};
 
 struct RcCol {
   uint64_t off, off2;  // bytes from the buffer start (row-wise: inside the row) of the slot / of AVG's count slot
@@ -55,45 +47,11 @@ struct RcDesc {
   RcCol col[HDK_HIP_MAX_TARGETS];
 };
 
-// the table is read once per pass and is larger than the last-level cache: every load is non-temporal (nt_load)
-HDK_DEV int64_t rc_load_sext(const int8_t* base, size_t off, uint32_t width) {
-  switch (width) {
-    case 1:
-      return nt_load<int8_t>(base, off);
-    case 2:
-      return nt_load<int16_t>(base, off);
-    case 4:
-      return nt_load<int32_t>(base, off);
-    default:
-      return nt_load<int64_t>(base, off);
-  }
-}
-
 // the `width` bytes at byte `off` of a 16-byte row held in registers, sign-extended (a slot never straddles a quad)
 HDK_DEV int64_t row16_word(const bf_i64x2& v, uint32_t off, uint32_t width) {
   const uint64_t q = static_cast<uint64_t>(off >= 8 ? v.y : v.x) >> ((off & 7u) * 8u);
   const uint32_t drop = 64u - 8u * width;
   return static_cast<int64_t>(q << drop) >> drop;
-}
-
-HDK_DEV int64_t rc_value(uint32_t op, int64_t a, int64_t b) {
-  if (op == RC_COPY) {
-    return a;
-  }
-  const int32_t fbits = static_cast<int32_t>(a);
-  if (op == RC_FLOAT || op == RC_FLOAT_NULLABLE) {
-    if (op == RC_FLOAT_NULLABLE && fbits == HDK_NULL_FLOAT_BITS) {
-      return HDK_NULL_DOUBLE_BITS;
-    }
-    return double_to_bits(static_cast<double>(__int_as_float(fbits)));
-  }
-  if (b == 0) {
-    return HDK_NULL_DOUBLE_BITS;
-  }
-  const double dividend = op == RC_AVG_INT      ? static_cast<double>(a)
-                          : op == RC_AVG_DOUBLE ? bits_to_double(a)
-                                                : static_cast<double>(__int_as_float(fbits));
-  return double_to_bits(dividend / static_cast<double>(b));
 }
 
 // Entry e of a tile belongs to thread e % kRcBlock, item e / kRcBlock: consecutive lanes read consecutive entries.
@@ -233,9 +191,8 @@ static void rc_desc_of(const hdk_hip_plan* p, uint32_t entry_count, const int64_
       c.stride = row_bytes;
       c.width = static_cast<uint32_t>(tg.slot_width);
     }
-    c.op = RC_COPY;
+    c.op = rc_op_of(tg);
     if (tg.agg == HDK_AGG_AVG) {
-      c.op = tg.arg_is_fp == HDK_FP_SLOT_FLOAT ? RC_AVG_FLOAT : tg.arg_is_fp ? RC_AVG_DOUBLE : RC_AVG_INT;
       c.width2 = static_cast<uint32_t>(tg.slot2_width);
       if (p->output_columnar) {
         c.off2 = columnar_slot_off(p, entry_count, s + 1);
@@ -244,8 +201,6 @@ static void rc_desc_of(const hdk_hip_plan* p, uint32_t entry_count, const int64_
         c.off2 = static_cast<uint64_t>(tg.slot2_off);
         c.stride2 = row_bytes;
       }
-    } else if (tg.arg_is_fp == HDK_FP_SLOT_FLOAT && tg.agg != HDK_AGG_COUNT && tg.agg != HDK_AGG_ID) {
-      c.op = tg.skip_null ? RC_FLOAT_NULLABLE : RC_FLOAT;
     }
     s += tg.agg == HDK_AGG_AVG ? 2 : 1;
   }

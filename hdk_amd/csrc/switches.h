@@ -52,6 +52,7 @@ namespace hdk {
   X(PROJECT_ONE_PASS)               \
   X(PROJECT_STATUS_SLACK)           \
   X(PROJECT_WRITER)                 \
+  X(ROWS_VARIANT)                   \
   X(S2_NO_PACKED_PAIR)              \
   X(S2_NO_Y)                        \
   X(SCATTER_BLOCKS_PER_CU)          \

@@ -25,8 +25,8 @@ from .hip_mgr import DeviceBuffer, HipMgr
 from .ir import QueryMustRunOnCpu, QueryUnit
 from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, GROUP_KINDS, JOIN_TYPES, ColumnDesc, CompiledPlan, Having, columnar_init_vals,
                    compact_init_vals, compile_query, describe_columns, eff_key_count, has_count_distinct, regroup_columns,
-                   group_windows, resolve_having_columns, resolve_join_columns, resolve_order_by, resolve_select_columns,
-                   resolve_window_columns, split_count_distinct, split_project_calls)
+                   group_windows, is_row_unit, resolve_having_columns, resolve_join_columns, resolve_order_by, resolve_select_columns,
+                   resolve_window_columns, split_count_distinct, split_project_calls, split_row_unit)
 from .storage import ArrowStorage
 
 
@@ -784,16 +784,21 @@ class PreparedStep:
 
     COLUMNS_ONE_CALL_BYTES = ONE_CALL_BYTES
 
-    def fetch_columns(self, stream_synced=False) -> DeviceColumns:
-        """The step's result as dense device columns (hdk_hip_columnarize_result): the buffer stays in HBM, only what
-        to_host() asks for crosses the link.  Group-by steps only (the library rejects projections and non-grouped
-        aggregates: HDK_HIP_ERR_UNSUPPORTED).  The device error code is checked as in fetch().
+    def fetch_columns(self, stream_synced=False, positions=False) -> DeviceColumns:
+        """The step's result as dense device columns: the buffer stays in HBM, only what to_host() asks for crosses the
+        link.  A group-by step goes through hdk_hip_columnarize_result, a projection or a non-grouped step through
+        hdk_hip_columnarize_rows (_fetch_row_columns).  The device error code is checked as in fetch().
         Sizing: when num_targets x entry_count x 8 is at most COLUMNS_ONE_CALL_BYTES (64 MiB) one call writes into a block
         of entry_count rows per column -- over-allocating a few MB costs less than a second pass over the table.  Above
         that the groups are counted first (out_cols = NULL: one streaming pass) and the block holds exactly row_count
-        rows per column: a half-empty 200 M-entry table then takes 1.6 GB, not 3.2 GB."""
-        err = self._error_code(stream_synced)
+        rows per column: a half-empty 200 M-entry table then takes 1.6 GB, not 3.2 GB.
+        `positions` (a projection only, else a ValueError): the row positions as a last column, "__pos"."""
         p = self.cp.plan
+        if positions and p.query_kind != A.Q_PROJECTION:
+            raise ValueError("positions=True: only a projection step has row positions")
+        err = self._error_code(stream_synced)
+        if p.query_kind in (A.Q_PROJECTION, A.Q_NON_GROUPED):
+            return self._fetch_row_columns(err, positions)
         n, nt = int(self.cp.entry_count), int(p.num_targets)
         iv = np.ascontiguousarray(self.cp.init_vals, dtype=np.int64)
 
@@ -803,6 +808,29 @@ class PreparedStep:
 
         block, capacity, rows = sized_columns(self.mgr, self.dev, nt, n, call, self.COLUMNS_ONE_CALL_BYTES)
         return DeviceColumns(self.cp, self.mgr, self.dev, block, capacity, rows, err)
+
+    def _fetch_row_columns(self, err: int, positions: bool) -> DeviceColumns:
+        """fetch_columns() of a projection or a non-grouped step (hdk_hip_columnarize_rows; the device form of the
+        reference's ColumnarResults::materializeAllColumnsProjection).  A projection's rows are the first
+        min(TOTAL_MATCHED, entry_count) of its buffer, which the library reads on the device: the worst case is
+        entry_count rows, and the one-call / count-first rule of fetch_columns applies (the count-only call reads one
+        word).  A non-grouped step is one call into a block of one row.  `err` < 0 (the step ran out of output rows, benign
+        under a LIMIT) travels in DeviceColumns.error_code."""
+        p = self.cp.plan
+        schema = describe_columns(self.cp, positions)
+        nc = len(schema)
+        projection = p.query_kind == A.Q_PROJECTION
+        n = int(self.cp.entry_count) if projection else 1
+        total = self.d_total_matched.ptr if projection else None
+
+        def call(out_ptr, capacity, row_count_ptr):
+            pos_ptr = out_ptr + (nc - 1) * capacity * 8 if (positions and out_ptr) else None
+            check(self.L.hdk_hip_columnarize_rows(C.byref(p), self.out_ptr, n, total, out_ptr, capacity, pos_ptr,
+                                                  row_count_ptr, self.dev, None))
+
+        one_call = self.COLUMNS_ONE_CALL_BYTES if projection else max(self.COLUMNS_ONE_CALL_BYTES, nc * 8)
+        block, capacity, rows = sized_columns(self.mgr, self.dev, nc, n, call, one_call)
+        return DeviceColumns(self.cp, self.mgr, self.dev, block, capacity, rows, err, schema)
 
     def run(self, stream=None) -> ExecutionResult:
         self.enqueue(stream)
@@ -987,13 +1015,16 @@ class Executor:
 
     def execute(self, q: QueryUnit, device_type: str = "GPU", frag_ids=None, result: str = "buffer", **kw):
         """-> ExecutionResult (the host copy of the buffer), or with result="columns" a DeviceColumns: the step's dense
-        columns in device memory (group-by steps; PreparedStep.fetch_columns)."""
+        columns in device memory (PreparedStep.fetch_columns).  On a projection or a non-grouped QueryUnit, result_joins,
+        windows, select and the SortInfo are taken off the unit (plan.split_row_unit) and applied to its columns."""
         if device_type != "GPU":
             raise QueryMustRunOnCpu("hdk_amd ships the GPU path only; run device_type='CPU' on HDK itself")
         if result not in ("buffer", "columns"):
             raise ValueError(f"result must be 'buffer' or 'columns', not {result!r}")
         sq = q.query if isinstance(q, CompiledPlan) else q
-        if sq.result_joins:
+        # a projection or a non-grouped unit: what compile_query refuses on it is applied to its dense columns below
+        row_unit = isinstance(q, QueryUnit) and is_row_unit(q)
+        if sq.result_joins and not row_unit:
             if result == "buffer":
                 raise ValueError("result_joins need result='columns': they join the dense result columns, not a hash-table buffer")
             if isinstance(q, CompiledPlan):
@@ -1018,6 +1049,13 @@ class Executor:
             raise ValueError("order_by / limit / offset need result='columns': a hash-table buffer has no row order")
         if sq.having and result == "buffer":
             raise ValueError("having needs result='columns': it filters the dense result columns, not a hash-table buffer")
+        if row_unit and (sq.result_joins or sq.windows or sq.select or sorts):
+            if sq.result_joins and result == "buffer":
+                raise ValueError("result_joins need result='columns': they join the dense result columns, not a hash-table buffer")
+            if (sq.limit is not None and sq.limit < 0) or sq.offset < 0:
+                raise ValueError("limit and offset must not be negative")
+            cols = self.execute(split_row_unit(sq), device_type, frag_ids, "columns", **kw)
+            return run_stages(cols, None, sq.windows, sq.select, sq.order_by, sq.limit, sq.offset, sq.result_joins)
         # A QueryUnit whose open-addressing table the PLANNER sized (no baseline_entry_count): running out of slots means
         # the estimate was wrong (stale statistics, a key from an inner column) -- RelAlgExecutor::handleOutOfMemoryRetry
         # (QE/RelAlgExecutor.cpp:1713-1747) re-runs with a doubled max_groups_buffer_entry_guess, at most twice more, and

@@ -186,6 +186,20 @@ inline void columnarize_result_on_device(const hdk_hip_plan& plan, const int64_t
                                    row_count_dev, workspace, workspace_bytes, device_id, nullptr));
 }
 
+// The same for a projection ResultSet or a non-grouped result on the device: what the ColumnarResults constructor would call
+// in place of materializeAllColumnsProjection with copyAllNonLazyColumns / materializeAllColumnsDirectly (ResultSetRegistry/
+// ColumnarResults.cpp:520-620).  `total_matched_dev` is the launch's TOTAL_MATCHED word (device memory; null for a
+// non-grouped result, whose entry_count is 1): the rows are the first min(max(*total_matched_dev, 0), entry_count) of the
+// buffer, in their order.  Column t starts at out_cols + t * capacity; pos_out (device, may be null; `capacity` rows)
+// receives the row positions; *row_count_dev always receives the true count.  No workspace; asynchronous on the device's
+// stream, the host never waits.
+inline void columnarize_rows_on_device(const hdk_hip_plan& plan, const int64_t* buffer, const uint32_t entry_count,
+                                       const int32_t* total_matched_dev, int64_t* out_cols, const size_t capacity,
+                                       int64_t* pos_out, uint64_t* row_count_dev, const int device_id) {
+  check(hdk_hip_columnarize_rows(&plan, buffer, entry_count, total_matched_dev, out_cols, static_cast<uint64_t>(capacity),
+                                 pos_out, row_count_dev, device_id, nullptr));
+}
+
 // ResultSet::sort for a result whose dense columns are on the device: what doBaselineSort (QueryEngine/ResultSetSort.cpp:
 // 64-188) does with ResultSetSortImpl.cu / TopKSort.cu.  `order` is RelAlgExecutionUnit::sort_info.order_entries restated
 // (col = tle_no - 1; is_fp / nullable / null_bits from the target's type), `limit` / `offset` are SortInfo's (0 = no

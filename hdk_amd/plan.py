@@ -337,16 +337,44 @@ class ColumnDesc:
     null_bits: int
     type: Type
     target_idx: int = -1
-    kind: str = "agg"  # 'key' | 'agg', as OutCol
+    kind: str = "agg"  # 'key' | 'agg' | 'proj', as OutCol
     agg: str = ""
     dictionary: Optional[list] = None
     scale: int = 0
 
 
-def describe_columns(cp: "CompiledPlan") -> List[ColumnDesc]:
+POSITIONS_COLUMN = "__pos"  # the row positions of a projection as a trailing dense column (fetch_columns(positions=True))
+
+
+def _describe_projection(cp: "CompiledPlan", positions: bool) -> List[ColumnDesc]:
+    """A projection's dense columns as hdk_hip_columnarize_rows writes them: one kind="proj" column per target, whose
+    NULL word is the argument's sentinel truncated to the slot's width and sign-extended -- the comparison
+    result_set._projection_columns makes.  A decimal keeps its scale: every decimal proj column is presented scaled."""
+    res = []
+    for oc in sorted(cp.out_cols, key=lambda c: c.target_idx):
+        tg = cp.plan.targets[oc.target_idx]
+        nullv = int(tg.arg.null_val)
+        w = cp.slot_widths[oc.target_idx]
+        if not tg.arg_is_fp and w < 8:
+            nullv = int(np.int64(nullv).astype({4: np.int32, 2: np.int16, 1: np.int8}[w]))
+        res.append(ColumnDesc(oc.name, bool(tg.arg_is_fp), bool(tg.arg.nullable), A.to_i64(nullv), oc.type, oc.target_idx,
+                              "proj", "", oc.dictionary, oc.scale))
+    if positions:
+        if any(d.name == POSITIONS_COLUMN for d in res):
+            raise ValueError(f"a target is already called {POSITIONS_COLUMN!r}: the positions column takes that name")
+        res.append(ColumnDesc(POSITIONS_COLUMN, False, False, 0, Type("int", 8, False), len(res), "proj"))
+    return res
+
+
+def describe_columns(cp: "CompiledPlan", positions: bool = False) -> List[ColumnDesc]:
     """The ColumnDesc of every dense column of a plan's result, by target index: result_set.dense_column_null and
-    cp.out_cols restated per column."""
+    cp.out_cols restated per column.  A projection's columns are described by _describe_projection; `positions` (a
+    projection only) appends its row positions as a last column."""
     from .result_set import dense_column_null
+    if cp.plan.query_kind == A.Q_PROJECTION:
+        return _describe_projection(cp, positions)
+    if positions:
+        raise ValueError("positions: only a projection has row positions")
     res = []
     for oc in sorted(cp.out_cols, key=lambda c: c.target_idx):
         is_fp, nullable, null_bits = dense_column_null(cp, oc.target_idx)
@@ -1871,6 +1899,34 @@ def init_buffer_host(cp: CompiledPlan, entry_count: Optional[int] = None) -> np.
         buf[:, :keys_quads] = kb.view(np.int64)
     buf[:, keys_quads:] = compact_init_vals(cp)[None, :]
     return buf.reshape(-1).copy()
+
+
+# ---------------------------------------------------------------------------------------------
+# A projection or a non-grouped unit with stages above it: the unit compile_query takes, and what follows on its columns
+# ---------------------------------------------------------------------------------------------
+def is_row_unit(q: QueryUnit) -> bool:
+    """A filter/project unit (every target a Proj) or a non-grouped aggregate (no GROUP BY, every target an Agg): the units
+    whose dense columns hdk_hip_columnarize_rows makes."""
+    from .ir import Proj
+    if not q.targets or has_count_distinct(q):
+        return False
+    if all(isinstance(t, Proj) for t in q.targets):
+        return True
+    return not q.groupby and all(isinstance(t, Agg) for t in q.targets)
+
+
+def split_row_unit(q: QueryUnit) -> QueryUnit:
+    """The unit below the result stages of a row unit: `q` without result_joins, windows, select and SortInfo, which
+    compile_query refuses on such a unit and Executor.execute(result="columns") applies to its dense columns instead.
+    `having` stays (compile_query refuses it: a WHERE does that job).  A projection with a LIMIT and nothing that
+    reorders, joins or looks across its rows (no order_by, windows or result_joins) gets scan_limit = offset + limit
+    unless it has one (the reference's get_scan_limit): the scan stops claiming rows and the buffer is sized by it."""
+    from .ir import Proj
+    inner = dataclasses.replace(q, result_joins=[], windows=[], select=[], order_by=[], limit=None, offset=0)
+    if isinstance(q.targets[0], Proj) and q.limit is not None and not (q.order_by or q.windows or q.result_joins) and \
+            not q.scan_limit and q.offset + q.limit > 0:
+        inner.scan_limit = int(q.offset) + int(q.limit)
+    return inner
 
 
 # ---------------------------------------------------------------------------------------------

@@ -257,6 +257,49 @@ def dense_to_columns(cp: CompiledPlan, dense: List[np.ndarray]) -> Dict[str, lis
     return described_to_columns(describe_columns(cp), dense)
 
 
+def rows_to_dense(cp: CompiledPlan, buf: np.ndarray, total_matched=None, positions: bool = False) -> List[np.ndarray]:
+    """hdk_hip_columnarize_rows stated in numpy over a host copy of the buffer: one array of int64 words per dense column
+    (describe_columns(cp, positions) describes them).  A projection: rows [0, min(max(total_matched, 0), entry_count)) of
+    the buffer in their order, every slot sign-extended from its width, the row positions last when asked for.  A
+    non-grouped result: one row; a float accumulator widened to double (NULL_FLOAT -> NULL_DOUBLE under skip_null), AVG
+    as double(sum) / double(count) with NULL_DOUBLE for count 0, everything else the slot as it is."""
+    p = cp.plan
+    buf = np.ascontiguousarray(buf)
+    if p.query_kind == A.Q_PROJECTION:
+        n = int(p.entry_count)
+        rows = min(max(int(total_matched), 0), n)
+        pos, cols = projection_arrays(cp, buf, rows, n)
+        cols = [np.ascontiguousarray(c, dtype=np.int64) for c in cols]
+        return cols + [np.ascontiguousarray(pos, dtype=np.int64)] if positions else cols
+    if p.query_kind != A.Q_NON_GROUPED:
+        raise ValueError("rows_to_dense takes projections and non-grouped results; a group-by buffer has empty entries")
+    if positions:
+        raise ValueError("positions: only a projection has row positions")
+    slots = buf.view(np.int64)
+    out, s = [], 0
+    for ti in range(p.num_targets):
+        tg = p.targets[ti]
+        a = slots[s:s + 1].copy()
+        float_slot = tg.arg_is_fp == A.FP_SLOT_FLOAT and tg.agg not in (A.AGG_COUNT, A.AGG_ID)
+        f32 = (a & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
+        if tg.agg == A.AGG_AVG:
+            cnt = int(slots[s + 1])
+            dividend = f32.astype(np.float64) if float_slot else a.view(np.float64) if tg.arg_is_fp else a.astype(np.float64)
+            with np.errstate(all="ignore"):
+                v = dividend / np.float64(cnt) if cnt else np.array([A.NULL_DOUBLE_BITS], dtype=np.int64).view(np.float64)
+            a = v.view(np.int64)
+            s += 2
+        else:
+            if float_slot:
+                if tg.skip_null and int(f32.view(np.uint32)[0]) == (A.NULL_FLOAT_BITS & 0xFFFFFFFF):
+                    a = np.array([A.NULL_DOUBLE_BITS], dtype=np.int64)
+                else:
+                    a = f32.astype(np.float64).view(np.int64)
+            s += 1
+        out.append(np.ascontiguousarray(a, dtype=np.int64))
+    return out
+
+
 def to_arrow(cp: CompiledPlan, buf: np.ndarray, entry_count=None, nrows=None):
     return columns_to_arrow(cp, to_columns(cp, buf, entry_count, nrows))
 
@@ -310,6 +353,9 @@ def described_to_arrow(schema, cols: Dict[str, list]):
         v = cols[d.name]
         if d.dictionary is not None and d.agg != "count":
             ty = pa.string()
+        elif d.kind == "proj":  # (columns_to_arrow's rule for a projected column: a decimal shows as the doubles it holds)
+            ty = pa.float64() if d.is_fp or any(isinstance(x, float) for x in v) else \
+                {1: pa.int8(), 2: pa.int16(), 4: pa.int32(), 8: pa.int64()}[d.type.size]
         elif d.is_fp or (d.scale and d.agg != "count"):
             ty = pa.float64()
         elif d.agg == "count":

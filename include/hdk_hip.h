@@ -617,6 +617,33 @@ int32_t hdk_hip_columnarize_result(const hdk_hip_plan* plan, const int64_t* buf,
                                    void* workspace, size_t workspace_bytes, int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Columnar results on the device: projections and non-grouped results.
+ * Replaces, for a ResultSet whose storage sits in HBM, ColumnarResults::materializeAllColumnsProjection with
+ * copyAllNonLazyColumns / materializeAllColumnsDirectly (omniscidb/ResultSetRegistry/ColumnarResults.cpp:520-620), which the
+ * reference runs on the host after copying the whole buffer.  The other half of the scan path (HDK_Q_PROJECTION or
+ * HDK_Q_NON_GROUPED; a group-by plan is HDK_HIP_ERR_UNSUPPORTED and goes through hdk_hip_columnarize_result) becomes the
+ * same dense form: one 8-byte column per target, column t at out_cols + t * capacity.
+ *   HDK_Q_PROJECTION   rows = min(max(*total_matched, 0), entry_count), read ON THE DEVICE (`total_matched` is the launch's
+ *                      TOTAL_MATCHED word; a step that ran out of output rows has total_matched > entry_count).  Row r of
+ *                      every column is buffer row r -- ResultSet iteration order; rows are never reordered.  Both layouts:
+ *                      row-wise [int64 row position | one 8-byte slot per target], copied as they are, and columnar
+ *                      [positions: entry_count x 8 | one column per target at its width 1 / 2 / 4 / 8, each start aligned
+ *                      to 8], a narrow slot SIGN-EXTENDED to 64 bits (a narrow NULL sentinel arrives sign-extended), a
+ *                      double's 8 bytes copied.  `pos_out` (device, `capacity` rows, or NULL) receives the row positions.
+ *   HDK_Q_NON_GROUPED  entry_count must be 1, total_matched and pos_out NULL; rows = 1.  Slot i is buf[i] (AVG owns two);
+ *                      one value per target by the rules hdk_hip_columnarize_result documents for a slot: a FLOAT
+ *                      accumulator widened to double (HDK_NULL_FLOAT_BITS -> HDK_NULL_DOUBLE_BITS under skip_null), AVG
+ *                      through pair_to_double (HDK_NULL_DOUBLE_BITS at count 0), anything else the slot.
+ * `*row_count` (device) always receives the TRUE row count; rows at or beyond `capacity` are not written and nothing outside
+ * [0, min(rows, capacity)) of a column or of pos_out is touched; buffer rows at or beyond that are not read.
+ * out_cols == NULL: count only (pos_out is not written either).  No workspace, no atomics.  Asynchronous on `stream`; the
+ * host never waits.
+ * ---------------------------------------------------------------------------------------- */
+int32_t hdk_hip_columnarize_rows(const hdk_hip_plan* plan, const int64_t* buf, uint32_t entry_count,
+                                 const int32_t* total_matched, int64_t* out_cols, uint64_t capacity, int64_t* pos_out,
+                                 uint64_t* row_count, int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * ORDER BY / LIMIT / OFFSET over dense result columns on the device.
  * Replaces, for a result whose columns sit in HBM, ResultSet::sort with doBaselineSort and its GPU sorts
  * (omniscidb/QueryEngine/ResultSetSort.cpp:64-188, ResultSetSortImpl.cu, TopKSort.cu); the order entries, limit and
