@@ -28,6 +28,10 @@ MAX_PROJECT_INPUTS = 8
 MAX_JOIN_COLUMNS_KEYS = 8  # hdk_hip_join_columns (MAX_JOIN_KEYS is the keyed storage-table join's)
 MAX_JOIN_COLUMNS_OUTS = 32
 JOIN_NULL_SAFE = 1  # hdk_hip_join_columns flags; its types are JOIN_INNER / JOIN_LEFT / JOIN_SEMI / JOIN_ANTI below
+MAX_SETOP_COLUMNS = 8
+MAX_SETOP_OUTS = 16
+CONCAT_TAG_FIRST = 1  # hdk_hip_concat_columns flags
+SETOP_UNION, SETOP_INTERSECT, SETOP_INTERSECT_ALL, SETOP_EXCEPT, SETOP_EXCEPT_ALL = range(5)  # hdk_hip_setop
 JOIN_NO_ROW = 0xFFFFFFFF  # rperm_out of an output row without a partner
 SORT_NO_SELECT = 1  # hdk_hip_sort_columns flags
 F_AND, F_OR, F_NOT = 64, 65, 66
@@ -225,6 +229,14 @@ class JoinOut(C.Structure):
     """hdk_hip_join_out: one output column of hdk_hip_join_columns: column `col` of the left (side 0) or right (side 1)
     block; null_bits is what a right out holds for a LEFT join's row without a partner."""
     _fields_ = [("side", C.c_uint8), ("pad_", C.c_uint8 * 3), ("col", C.c_int32), ("null_bits", C.c_int64)]
+
+
+class SetopCol(C.Structure):
+    """hdk_hip_setop_col: one column pair of hdk_hip_concat_columns: left column lcol and right column rcol become one output
+    column; a word that is NULL on its side (side nullable, word equal to that side's null_bits) is written as
+    out_null_bits."""
+    _fields_ = [("lcol", C.c_int32), ("rcol", C.c_int32), ("lnullable", C.c_uint8), ("rnullable", C.c_uint8),
+                ("pad_", C.c_uint8 * 6), ("lnull_bits", C.c_int64), ("rnull_bits", C.c_int64), ("out_null_bits", C.c_int64)]
 
 
 class KernelOptions(C.Structure):

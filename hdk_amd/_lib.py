@@ -91,6 +91,11 @@ SIGNATURES = {
     "hdk_hip_join_columns_workspace_bytes": (sz, [C.c_uint64]),
     "hdk_hip_join_columns": (i32, [v, C.c_uint64, i32, C.c_uint64, v, C.c_uint64, i32, C.c_uint64, C.POINTER(A.JoinKey), i32,
                                    i32, u32, C.POINTER(A.JoinOut), i32, v, C.c_uint64, v, v, v, v, sz, i32, v]),
+    "hdk_hip_concat_columns": (i32, [v, C.c_uint64, i32, C.c_uint64, v, C.c_uint64, i32, C.c_uint64, C.POINTER(A.SetopCol), i32, i32,
+                                     u32, v, C.c_uint64, i32, v]),
+    "hdk_hip_setop_columns_workspace_bytes": (sz, [C.c_uint64]),
+    "hdk_hip_setop_columns": (i32, [v, C.c_uint64, i32, C.c_uint64, C.POINTER(i32), i32, i32, i32, C.POINTER(i32), i32, v,
+                                    C.c_uint64, v, v, sz, i32, v]),
     "hdk_hip_exchange_shape_for": (i32, [C.POINTER(A.Plan), C.POINTER(A.KernelOptions), i32, u32, i32,
                                          C.POINTER(A.ExchangeShape)]),
     "hdk_hip_scatter_to_owners": (i32, [C.POINTER(A.Plan), C.POINTER(v), C.POINTER(A.KernelOptions),
@@ -130,6 +135,7 @@ EXTRA_SIGNATURES = {
     "hdk_hip_sizeof_project_out": (sz, []),
     "hdk_hip_sizeof_join_key": (sz, []),
     "hdk_hip_sizeof_join_out": (sz, []),
+    "hdk_hip_sizeof_setop_col": (sz, []),
 }
 
 

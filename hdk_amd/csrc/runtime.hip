@@ -478,5 +478,6 @@ size_t hdk_hip_sizeof_project_op(void) { return sizeof(hdk_hip_project_op); }
 size_t hdk_hip_sizeof_project_out(void) { return sizeof(hdk_hip_project_out); }
 size_t hdk_hip_sizeof_join_key(void) { return sizeof(hdk_hip_join_key); }
 size_t hdk_hip_sizeof_join_out(void) { return sizeof(hdk_hip_join_out); }
+size_t hdk_hip_sizeof_setop_col(void) { return sizeof(hdk_hip_setop_col); }
 
 }  // extern "C"

@@ -22,11 +22,11 @@ from . import _abi as A
 from . import result_set
 from ._lib import HdkHipError, check, lib, sync_switches
 from .hip_mgr import DeviceBuffer, HipMgr
-from .ir import QueryMustRunOnCpu, QueryUnit
-from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, GROUP_KINDS, JOIN_TYPES, ColumnDesc, CompiledPlan, Having, columnar_init_vals,
-                   compact_init_vals, compile_query, describe_columns, eff_key_count, has_count_distinct, regroup_columns,
+from .ir import QueryMustRunOnCpu, QueryUnit, Type
+from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, GROUP_KINDS, JOIN_TYPES, SETOP_CODES, SETOP_NAMES, ColumnDesc,
+                   CompiledPlan, Having, columnar_init_vals, compact_init_vals, compile_query, describe_columns, eff_key_count, has_count_distinct, regroup_columns,
                    group_windows, is_row_unit, resolve_having_columns, resolve_join_columns, resolve_order_by, resolve_select_columns,
-                   resolve_window_columns, split_count_distinct, split_project_calls, split_row_unit)
+                   resolve_setop_columns, resolve_window_columns, split_count_distinct, split_project_calls, split_row_unit)
 from .storage import ArrowStorage
 
 
@@ -149,12 +149,14 @@ def _stage(cols, apply, keep=None):
             cols.free()
 
 
-def run_stages(cols, having=None, windows=(), select=(), order_by=(), limit=None, offset=0, joins=()):
+def run_stages(cols, having=None, windows=(), select=(), order_by=(), limit=None, offset=0, joins=(), setops=()):
     """What a unit asks for above its GROUP BY, applied where the columns are: the joins with other results (ir.ResultJoin,
     in order; their right sides are not consumed), then HAVING (a plan.Having or conditions), which may read a joined
-    column, the window functions, which may read what HAVING kept, the select list, which may read a window column, then
-    the SortInfo, which names the columns it meets.  Consumes `cols`: each stage reads the result of the one before, whose
-    block is handed back, also when a stage raises.  -> the last result; `cols` itself when nothing applies."""
+    column, the window functions, which may read what HAVING kept, the select list, which may read a window column, the
+    set operations with other results (ir.ResultSetOp, in order; their right sides are not consumed), then the SortInfo,
+    which names the columns it meets and orders the COMBINED rows.  Consumes `cols`: each stage reads the result of the
+    one before, whose block is handed back, also when a stage raises.  -> the last result; `cols` itself when nothing
+    applies."""
     for j in joins:
         cols = _stage(cols, lambda c: c.join(j.right, j.left_on, j.right_on, j.type, j.null_safe, j.right_cols))
     if having:
@@ -163,6 +165,8 @@ def run_stages(cols, having=None, windows=(), select=(), order_by=(), limit=None
         cols = _stage(cols, lambda c: c.windows(windows))
     if select:
         cols = _stage(cols, lambda c: c.project(select))
+    for so in setops:
+        cols = _stage(cols, lambda c: c.setop(so.right, so.op, so.all))
     if order_by or limit is not None or offset:
         cols = _stage(cols, lambda c: c.sort(order_by, limit, offset))
     return cols
@@ -517,6 +521,103 @@ class DeviceColumns:
             if rsrc is not right:
                 rsrc.free()
         return out
+
+    SETOP_ONE_CALL_BYTES = ONE_CALL_BYTES
+
+    def _concat(self, first: "DeviceColumns", second: "DeviceColumns", pairs, block: DeviceBuffer, capacity: int,
+                side_col: int = -1, flags: int = 0):
+        """hdk_hip_concat_columns: the rows of `first`, then those of `second`, into `block`; `pairs` as
+        plan.resolve_setop_columns gives them for (first, second)"""
+        arr = (A.SetopCol * len(pairs))()
+        for j, (lc, rc, ln, rn, lbits, rbits, obits) in enumerate(pairs):
+            arr[j] = A.SetopCol(lc, rc, int(ln), int(rn), (C.c_uint8 * 6)(), A.to_i64(lbits), A.to_i64(rbits), A.to_i64(obits))
+        check(lib().hdk_hip_concat_columns(first.block.ptr if first.num_rows else None, first.capacity if first.num_rows else 0,
+                                           first.num_cols, first.num_rows,
+                                           second.block.ptr if second.num_rows else None,
+                                           second.capacity if second.num_rows else 0, second.num_cols, second.num_rows, arr,
+                                           len(pairs), side_col, flags, block.ptr, capacity, self.device_id, None))
+
+    def _setop(self, other: "DeviceColumns", op: str, all: bool) -> "DeviceColumns":
+        if other.device_id != self.device_id:
+            raise ValueError("the two sides of a set operation live on different devices")
+        pairs, descs = resolve_setop_columns(self.schema, other.schema)
+        out = self._like(None, 0, 0, descs)
+        nc, nl, nr = len(pairs), self.num_rows, other.num_rows
+        if nl + nr >= 1 << 32:
+            raise QueryMustRunOnCpu(f"a set operation over {nl} + {nr} rows: the library's row indices are 32 bits wide")
+        if nl + nr == 0 or (nl == 0 and op != "union"):
+            return out  # (without a left row INTERSECT and EXCEPT keep nothing)
+        if nl:
+            self._block_ptr()
+        if nr:
+            other._block_ptr()
+        n = nl + nr
+        if op == "union" and all:
+            block = self.mgr.alloc(nc * n * 8, self.device_id)
+            try:
+                self._concat(self, other, pairs, block, n)
+                self.mgr.synchronizeStream(self.device_id)
+            except Exception:
+                block.free()
+                raise
+            out.block, out.capacity, out.num_rows = block, n, n
+            return out
+        # the right rows FIRST and a tag that is 1 on them: the stable sort then leaves every run with its right rows in front
+        swapped = [(rc, lc, rn, ln, rbits, lbits, obits) for lc, rc, ln, rn, lbits, rbits, obits in pairs]
+        tag = ColumnDesc("__side", False, False, 0, Type("int", 8, False), nc, "proj")
+        tagged = DeviceColumns(self.compiled, self.mgr, self.device_id, self.mgr.alloc((nc + 1) * n * 8, self.device_id), n, n,
+                               schema=descs + [tag])
+        ordered = None
+        try:
+            self._concat(other, self, swapped, tagged.block, n, nc, A.CONCAT_TAG_FIRST)
+            ordered = tagged.sort([(t, False, False) for t in range(nc)])
+            tagged.free()
+            idx = (C.c_int32 * nc)(*range(nc))
+            src = ordered.block.ptr
+
+            def call(out_ptr, capacity, row_count_ptr):
+                check(lib().hdk_hip_setop_columns(src, n, nc + 1, n, idx, nc, nc, SETOP_CODES[(op, bool(all))], idx, nc, out_ptr,
+                                                  capacity, row_count_ptr, None, 0, self.device_id, None))
+
+            out.block, out.capacity, out.num_rows = sized_columns(self.mgr, self.device_id, nc, n if op == "union" else nl, call,
+                                                                  self.SETOP_ONE_CALL_BYTES, drop_empty=True)
+        finally:
+            tagged.free()
+            if ordered is not None:
+                ordered.free()
+        return out
+
+    def union(self, other: "DeviceColumns", all: bool = False) -> "DeviceColumns":
+        """UNION [ALL] of these rows (the left operand) with `other`'s on the device -> a new DeviceColumns that carries its
+        own schema (plan.resolve_setop_columns: columns pair by position, names and presentation from this side, NULLs of
+        both sides rewritten to one sentinel per column); both inputs stay valid and the result owns an exactly sized block
+        (up to 64 MiB of worst-case output one call writes a block of the worst-case row count, as filter() does).  Whole
+        rows are compared word by word: NULL equals NULL, -0.0 differs from +0.0, doubles included.
+        all=True is one hdk_hip_concat_columns call: this object's rows, then `other`'s, each in its order.
+        Otherwise (and for intersect / except_) the right rows are concatenated in front of the left rows with a side
+        column, sorted on all columns ascending with NULLs last (hdk_hip_sort_columns, stable), and hdk_hip_setop_columns
+        keeps one row per distinct row; the side column never leaves.  The rows therefore come out ASCENDING in the device
+        sort's order over all columns, NULLs last.  2^32 or more rows on both sides together must run on the CPU, which is
+        found before anything is allocated; temporaries are handed back on every path."""
+        return self._setop(other, "union", all)
+
+    def intersect(self, other: "DeviceColumns", all: bool = False) -> "DeviceColumns":
+        """INTERSECT [ALL] on the device: the rows of this object that `other` holds too -- once each, or with all=True
+        min(l, r) copies of a row that is l times here and r times there.  Schema, comparison, method, output order and
+        sizing as union() (the worst case is this object's rows)."""
+        return self._setop(other, "intersect", all)
+
+    def except_(self, other: "DeviceColumns", all: bool = False) -> "DeviceColumns":
+        """EXCEPT [ALL] on the device: the rows of this object that `other` does not hold -- once each, or with all=True
+        max(l - r, 0) copies of a row that is l times here and r times there.  Schema, comparison, method, output order and
+        sizing as union() (the worst case is this object's rows)."""
+        return self._setop(other, "except", all)
+
+    def setop(self, other: "DeviceColumns", op: str, all: bool = False) -> "DeviceColumns":
+        """union / intersect / except_ by name (ir.ResultSetOp.op)"""
+        if op not in SETOP_NAMES:
+            raise ValueError(f"set operation {op!r} (union, intersect or except)")
+        return self._setop(other, op, all)
 
     def free(self):
         if self.block is not None:
@@ -1016,7 +1117,7 @@ class Executor:
     def execute(self, q: QueryUnit, device_type: str = "GPU", frag_ids=None, result: str = "buffer", **kw):
         """-> ExecutionResult (the host copy of the buffer), or with result="columns" a DeviceColumns: the step's dense
         columns in device memory (PreparedStep.fetch_columns).  On a projection or a non-grouped QueryUnit, result_joins,
-        windows, select and the SortInfo are taken off the unit (plan.split_row_unit) and applied to its columns."""
+        result_setops, windows, select and the SortInfo are taken off the unit (plan.split_row_unit) and applied to its columns."""
         if device_type != "GPU":
             raise QueryMustRunOnCpu("hdk_amd ships the GPU path only; run device_type='CPU' on HDK itself")
         if result not in ("buffer", "columns"):
@@ -1024,17 +1125,20 @@ class Executor:
         sq = q.query if isinstance(q, CompiledPlan) else q
         # a projection or a non-grouped unit: what compile_query refuses on it is applied to its dense columns below
         row_unit = isinstance(q, QueryUnit) and is_row_unit(q)
-        if sq.result_joins and not row_unit:
-            if result == "buffer":
+        if sq.result_setops and result == "buffer":
+            raise ValueError("result_setops need result='columns': they combine the dense result columns, not a hash-table buffer")
+        if (sq.result_joins or sq.result_setops) and not row_unit:
+            if sq.result_joins and result == "buffer":
                 raise ValueError("result_joins need result='columns': they join the dense result columns, not a hash-table buffer")
             if isinstance(q, CompiledPlan):
-                raise ValueError("result_joins are applied above compile_query: execute the QueryUnit itself")
+                raise ValueError("result_joins and result_setops are applied above compile_query: execute the QueryUnit itself")
             if not has_count_distinct(sq):
                 # what follows the joins may name a joined column: the unit below them is compiled without it
-                inner = dataclasses.replace(sq, result_joins=[], having=[], windows=[], select=[], order_by=[], limit=None,
-                                            offset=0)
+                inner = dataclasses.replace(sq, result_joins=[], result_setops=[], having=[], windows=[], select=[], order_by=[],
+                                            limit=None, offset=0)
                 cols = self.execute(inner, device_type, frag_ids, "columns", **kw)
-                return run_stages(cols, sq.having, sq.windows, sq.select, sq.order_by, sq.limit, sq.offset, sq.result_joins)
+                return run_stages(cols, sq.having, sq.windows, sq.select, sq.order_by, sq.limit, sq.offset, sq.result_joins,
+                                  sq.result_setops)
         if sq.windows and result == "buffer":
             raise ValueError("windows need result='columns': they read the dense result columns, not a hash-table buffer")
         if sq.select and result == "buffer":
@@ -1049,13 +1153,14 @@ class Executor:
             raise ValueError("order_by / limit / offset need result='columns': a hash-table buffer has no row order")
         if sq.having and result == "buffer":
             raise ValueError("having needs result='columns': it filters the dense result columns, not a hash-table buffer")
-        if row_unit and (sq.result_joins or sq.windows or sq.select or sorts):
+        if row_unit and (sq.result_joins or sq.result_setops or sq.windows or sq.select or sorts):
             if sq.result_joins and result == "buffer":
                 raise ValueError("result_joins need result='columns': they join the dense result columns, not a hash-table buffer")
             if (sq.limit is not None and sq.limit < 0) or sq.offset < 0:
                 raise ValueError("limit and offset must not be negative")
             cols = self.execute(split_row_unit(sq), device_type, frag_ids, "columns", **kw)
-            return run_stages(cols, None, sq.windows, sq.select, sq.order_by, sq.limit, sq.offset, sq.result_joins)
+            return run_stages(cols, None, sq.windows, sq.select, sq.order_by, sq.limit, sq.offset, sq.result_joins,
+                              sq.result_setops)
         # A QueryUnit whose open-addressing table the PLANNER sized (no baseline_entry_count): running out of slots means
         # the estimate was wrong (stale statistics, a key from an inner column) -- RelAlgExecutor::handleOutOfMemoryRetry
         # (QE/RelAlgExecutor.cpp:1713-1747) re-runs with a doubled max_groups_buffer_entry_guess, at most twice more, and
@@ -1086,4 +1191,5 @@ class Executor:
         inner, rg = split_count_distinct(q)
         cols = self.execute(inner, frag_ids=frag_ids, result="columns", **kw)
         out = _stage(cols, lambda c: c.group_by(rg.keys, rg.outs))
-        return run_stages(out, rg.having, rg.windows, rg.select, rg.order_by, rg.limit, rg.offset, q.result_joins)
+        return run_stages(out, rg.having, rg.windows, rg.select, rg.order_by, rg.limit, rg.offset, q.result_joins,
+                          q.result_setops)

@@ -320,4 +320,36 @@ inline void join_columns_on_device(const int64_t* lcols, const size_t lcapacity,
                              rperm_out, workspace, workspace_bytes, device_id, nullptr));
 }
 
+// Set operations of two results that sit in HBM: the device form of LogicalUnion over two previous steps' results
+// (RelAlgExecutor::executeUnion, QueryEngine/RelAlgExecutor.cpp), widened to INTERSECT [ALL] and EXCEPT [ALL].
+// concat_columns_on_device is UNION ALL: the left rows, then the right rows, each side's in-band NULL rewritten to
+// pairs[j].out_null_bits; side_col >= 0 adds a column that holds 0 for left and 1 for right rows (HDK_HIP_CONCAT_TAG_FIRST in
+// `flags`: 1 and 0).  setop_columns_on_device walks ONE block in which equal rows are adjacent and, inside a run, the rows
+// with a non-zero word in `tag_col` precede the rows with tag 0 -- what a stable hdk_hip_sort_columns on all compared
+// columns makes of a block whose RIGHT operand was concatenated first with HDK_HIP_CONCAT_TAG_FIRST -- and writes the rows
+// that `op` (a hdk_hip_setop) keeps, in input order, column j at out_cols + j * out_capacity.  *row_count_dev (device)
+// always receives the true number of kept rows, rows at or beyond out_capacity are not written, out_cols == nullptr counts
+// only.  `workspace` comes from the BufferProvider (setop_columns_workspace_bytes(num_rows) bytes) or is null (the stream's
+// memory pool).  Both are asynchronous on the device's stream: the host never waits.
+inline void concat_columns_on_device(const int64_t* lcols, const size_t lcapacity, const int lnum_cols, const size_t lnum_rows,
+                                     const int64_t* rcols, const size_t rcapacity, const int rnum_cols, const size_t rnum_rows,
+                                     const hdk_hip_setop_col* pairs, const int num_cols, const int side_col, const uint32_t flags,
+                                     int64_t* out_cols, const size_t out_capacity, const int device_id) {
+  check(hdk_hip_concat_columns(lcols, static_cast<uint64_t>(lcapacity), lnum_cols, static_cast<uint64_t>(lnum_rows), rcols,
+                               static_cast<uint64_t>(rcapacity), rnum_cols, static_cast<uint64_t>(rnum_rows), pairs, num_cols,
+                               side_col, flags, out_cols, static_cast<uint64_t>(out_capacity), device_id, nullptr));
+}
+inline size_t setop_columns_workspace_bytes(const size_t num_rows) {
+  return hdk_hip_setop_columns_workspace_bytes(static_cast<uint64_t>(num_rows));
+}
+inline void setop_columns_on_device(const int64_t* cols, const size_t capacity, const int num_cols, const size_t num_rows,
+                                    const int32_t* key_cols, const int num_keys, const int tag_col, const int op,
+                                    const int32_t* out_cols_idx, const int num_outs, int64_t* out_cols, const size_t out_capacity,
+                                    uint64_t* row_count_dev, int8_t* workspace, const size_t workspace_bytes,
+                                    const int device_id) {
+  check(hdk_hip_setop_columns(cols, static_cast<uint64_t>(capacity), num_cols, static_cast<uint64_t>(num_rows), key_cols, num_keys,
+                              tag_col, op, out_cols_idx, num_outs, out_cols, static_cast<uint64_t>(out_capacity), row_count_dev,
+                              workspace, workspace_bytes, device_id, nullptr));
+}
+
 }  // namespace hip_rt

@@ -288,6 +288,17 @@ class ResultJoin:
     right_cols: Optional[Sequence] = None
 
 
+@dataclass(frozen=True, eq=False)
+class ResultSetOp:
+    """A set operation of the unit's result columns (the LEFT operand) with another result that already sits on the device
+    (the reference's LogicalUnion over two previous steps' results, widened to SQL's other set operations): `right` is an
+    executor.DeviceColumns, which is not consumed; `op` is union, intersect or except; `all` keeps duplicates (UNION ALL,
+    INTERSECT ALL, EXCEPT ALL).  Columns pair by position and whole rows are compared (plan.resolve_setop_columns)."""
+    right: object
+    op: str
+    all: bool = False
+
+
 @dataclass
 class QueryUnit:
     """What one execution step needs (cf. RelAlgExecutionUnit)."""
@@ -317,6 +328,11 @@ class QueryUnit:
     # on the device after HAVING and the windows and before order_by / limit / offset (result="columns"), whose entries then
     # name the PROJECTED columns.  The result holds these columns only.  Empty: every column as it is
     select: List["Proj"] = field(default_factory=list)
+    # set operations of the result columns with other device results (the unit's result is the left operand), applied on
+    # the device in order after the select list and before order_by / limit / offset, which then apply to the COMBINED
+    # rows, as a compound query's ORDER BY does (result="columns").  It stands before result_joins, which
+    # stays the last field
+    result_setops: List[ResultSetOp] = field(default_factory=list)
     # joins of the result columns with other device results, applied on the device FIRST, in order (result="columns"):
     # having, windows, select and order_by may then name a joined column
     result_joins: List[ResultJoin] = field(default_factory=list)

@@ -533,6 +533,53 @@ def resolve_join_columns(left: List[ColumnDesc], right: List[ColumnDesc], left_o
     return keys, outs, descs
 
 
+SETOP_CODES = {("union", False): A.SETOP_UNION, ("intersect", False): A.SETOP_INTERSECT,
+               ("intersect", True): A.SETOP_INTERSECT_ALL, ("except", False): A.SETOP_EXCEPT,
+               ("except", True): A.SETOP_EXCEPT_ALL}  # (UNION ALL is hdk_hip_concat_columns alone)
+SETOP_NAMES = ("union", "intersect", "except")
+
+
+def resolve_setop_columns(left: List[ColumnDesc], right: List[ColumnDesc]) -> Tuple[List[tuple], List[ColumnDesc]]:
+    """The schema rule of a set operation (UNION / INTERSECT / EXCEPT) of two results, after the model of
+    resolve_join_columns: -> (one (left column, right column, lnullable, rnullable, lnull_bits, rnull_bits,
+    out_null_bits) per column -- hdk_hip_setop_col's fields --, the ColumnDesc of every output).  Columns pair BY
+    POSITION; names and the presentation fields (type, dictionary, scale, kind) come from the left.  An output column is
+    nullable when either side is.  Its in-band NULL is the left's, except that when both sides are nullable with
+    different sentinels, or only the right side is, it is the 8-byte type's sentinel (NULL_BIGINT, NULL_DOUBLE's bits
+    for fp), to which the concatenation rewrites the NULLs of both sides.  A non-NULL word that equals the chosen sentinel
+    reads as NULL afterwards: the project's in-band rule, as for every dense column.  A ValueError: different column
+    counts or none, an fp column paired with one that is not (whole rows are compared word by word), decimal scales that
+    differ, dictionary columns whose dictionaries are not the same list (ids of different dictionaries do not compare).
+    More columns than the library compares in one call must run on the CPU."""
+    if len(left) != len(right) or not left:
+        raise ValueError(f"a set operation needs the same number of columns on both sides and at least one: {len(left)} left, "
+                         f"{len(right)} right")
+    if len(left) > A.MAX_SETOP_COLUMNS:
+        raise QueryMustRunOnCpu("a set operation over more than %d columns" % A.MAX_SETOP_COLUMNS)
+    pairs, descs = [], []
+    for t, (a, b) in enumerate(zip(left, right)):
+        if bool(a.is_fp) != bool(b.is_fp):
+            raise ValueError(f"set operation column {t} ({a.name} / {b.name}): a floating-point column is paired with one that is "
+                             "not; whole rows are compared word by word")
+        if (a.scale or 0) != (b.scale or 0) or (a.type.kind == "decimal") != (b.type.kind == "decimal") or \
+                (a.type.kind == "decimal" and a.type.scale != b.type.scale):
+            raise ValueError(f"set operation column {t} ({a.name} / {b.name}): the decimal scales differ")
+        a_dict, b_dict = a.dictionary is not None or a.type.kind == "dict", b.dictionary is not None or b.type.kind == "dict"
+        if a_dict or b_dict:
+            if not (a_dict and b_dict) or a.dictionary is None or (a.dictionary is not b.dictionary and a.dictionary != b.dictionary):
+                raise ValueError(f"set operation column {t} ({a.name} / {b.name}): the columns are not ids of the same dictionary, "
+                                 "so equal ids do not mean equal strings")
+        nullable = bool(a.nullable or b.nullable)
+        if (a.nullable and b.nullable and A.to_i64(a.null_bits) != A.to_i64(b.null_bits)) or (b.nullable and not a.nullable):
+            out_null = A.to_i64(A.NULL_DOUBLE_BITS if a.is_fp else A.NULL_BIGINT)
+        else:
+            out_null = A.to_i64(a.null_bits)
+        pairs.append((t, t, bool(a.nullable), bool(b.nullable), A.to_i64(a.null_bits), A.to_i64(b.null_bits), out_null))
+        ty = a.type if a.type.nullable == nullable else a.type.with_nullable(nullable)
+        descs.append(dataclasses.replace(a, nullable=nullable, null_bits=out_null, type=ty, target_idx=t))
+    return pairs, descs
+
+
 WINDOW_RANKING = ("row_number", "rank", "dense_rank", "percent_rank", "cume_dist", "ntile")
 WINDOW_AGGREGATES = ("avg", "min", "max", "sum", "count")
 
@@ -1458,6 +1505,9 @@ def compile_query(storage: ArrowStorage, q: QueryUnit) -> CompiledPlan:
     if q.result_joins:
         raise ValueError("result_joins are applied above compile_query: compile the unit without them and join its dense "
                          "columns (Executor.execute(result='columns') does both)")
+    if q.result_setops:
+        raise ValueError("result_setops are applied above compile_query: compile the unit without them and combine its dense "
+                         "columns (Executor.execute(result='columns') does both)")
     if q.limit is not None and q.limit < 0 or q.offset < 0:
         raise ValueError("limit and offset must not be negative")
     if q.targets and all(isinstance(t, Proj) for t in q.targets):
@@ -1922,8 +1972,9 @@ def split_row_unit(q: QueryUnit) -> QueryUnit:
     reorders, joins or looks across its rows (no order_by, windows or result_joins) gets scan_limit = offset + limit
     unless it has one (the reference's get_scan_limit): the scan stops claiming rows and the buffer is sized by it."""
     from .ir import Proj
-    inner = dataclasses.replace(q, result_joins=[], windows=[], select=[], order_by=[], limit=None, offset=0)
-    if isinstance(q.targets[0], Proj) and q.limit is not None and not (q.order_by or q.windows or q.result_joins) and \
+    inner = dataclasses.replace(q, result_joins=[], result_setops=[], windows=[], select=[], order_by=[], limit=None, offset=0)
+    if isinstance(q.targets[0], Proj) and q.limit is not None and \
+            not (q.order_by or q.windows or q.result_joins or q.result_setops) and \
             not q.scan_limit and q.offset + q.limit > 0:
         inner.scan_limit = int(q.offset) + int(q.limit)
     return inner
@@ -1990,6 +2041,6 @@ def split_count_distinct(q: QueryUnit) -> Tuple[QueryUnit, Regroup]:
         else:
             raise ValueError(f"unknown aggregate {t.kind!r}")
     inner = dataclasses.replace(q, groupby=list(q.groupby) + [arg], targets=inner_targets, order_by=[], limit=None, offset=0,
-                                having=[], windows=[], select=[], result_joins=[])
+                                having=[], windows=[], select=[], result_joins=[], result_setops=[])
     return inner, Regroup(list(range(nk)), outs, list(q.having), list(q.order_by), q.limit, q.offset, list(q.windows),
                           list(q.select))

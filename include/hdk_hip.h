@@ -1067,6 +1067,101 @@ int32_t hdk_hip_join_columns(const int64_t* lcols, uint64_t lcapacity, int32_t l
                              size_t workspace_bytes, int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Set operations over dense result columns on the device: UNION ALL as one copy, and UNION / INTERSECT [ALL] / EXCEPT [ALL]
+ * as one walk over sorted runs.
+ * The device form, for results whose columns sit in HBM, of the reference's LogicalUnion step over two previous steps'
+ * results (RelAlgExecutor::executeUnion, omniscidb/QueryEngine/RelAlgExecutor.cpp), widened to SQL's other set operations.
+ * Rows are compared as WHOLE rows, word by word, doubles included.
+ *
+ * hdk_hip_concat_columns -- UNION ALL.
+ * Inputs: two blocks of dense columns, left (`lnum_cols` columns of `lnum_rows` 8-byte words, column t at
+ * lcols + t * lcapacity) and right (the same with r), NULLs in band -- what the other *_columns calls write.  The columns of
+ * a side without rows may be NULL.  `pairs`: `num_cols` (1..HDK_HIP_MAX_SETOP_COLUMNS) pairs of a left and a right column.
+ * Output: rows [0, lnum_rows) are the left rows and rows [lnum_rows, lnum_rows + rnum_rows) the right rows, both in input
+ * order.  A word that is NULL on its side (the side is nullable and the word EQUALS that side's null_bits, a bit compare) is
+ * written as out_null_bits; every other word is written unchanged -- so a non-NULL word that equals out_null_bits reads as
+ * NULL afterwards, the in-band rule of every *_columns call.  side_col < 0: pair j is output column j at
+ * out_cols + j * out_capacity.  side_col in [0, num_cols]: the output has num_cols + 1 columns, column side_col receives 0
+ * for every left row and 1 for every right row (with HDK_HIP_CONCAT_TAG_FIRST in `flags`: 1 for the left rows and 0 for the
+ * right rows, the tag hdk_hip_setop_columns expects when ITS right operand is passed here as the left block), and pair j is
+ * output column j + (j >= side_col).  Nothing outside rows [0, lnum_rows + rnum_rows) of an output column is touched.
+ * ASYNCHRONOUS on `stream`: one launch, no workspace; the host never waits.  The inputs are not modified and may overlap each
+ * other; out_cols may overlap neither.
+ * Errors, all found before any device is touched (HDK_HIP_ERR_INVALID_ARG with a message): a NULL pairs / out_cols (lcols or
+ * rcols with rows on that side), lnum_cols or rnum_cols < 1, num_cols outside 1..8, a column index outside its side's columns,
+ * side_col > num_cols, an unknown flag, lnum_rows + rnum_rows >= 2^32, rows > capacity, out_capacity below
+ * lnum_rows + rnum_rows, out_cols overlapping an input.
+ * Both sides empty: nothing is launched.
+ *
+ * hdk_hip_setop_columns -- the rows that a set operation keeps, over ONE block that holds the rows of both operands and a tag.
+ * Input: `num_cols` columns of `num_rows` 8-byte words, column t at cols + t * capacity.  key_cols[num_keys]
+ * (1..HDK_HIP_MAX_SETOP_COLUMNS) are the compared columns; a word of column `tag_col` (not a key) that is NOT 0 marks a row of
+ * the RIGHT operand, a 0 a row of the LEFT operand.  A RUN is a maximal stretch of adjacent rows that are BIT-EQUAL on every
+ * key column -- exactly the equivalence of hdk_hip_group_columns: NULL equals NULL, -0.0 differs from +0.0, NaNs are compared
+ * by pattern.
+ * PRECONDITION (as hdk_hip_group_columns and hdk_hip_join_columns have theirs): equal rows are ADJACENT, and inside a run the
+ * rows with a non-zero tag word PRECEDE the rows with tag 0.  hdk_hip_sort_columns (stable: ties keep their input order) on
+ * all key columns of a block whose right rows were concatenated FIRST establishes it.  A block that violates it is not an
+ * error and gives unspecified rows; even then nothing outside the permitted output range is written, *row_count is the number
+ * of rows the write pass emits and is at most num_rows: both passes read the same stored per-row keep bits.
+ * With rb = the right rows and lb = the left rows BEFORE a row in its run, the row is kept iff
+ *   HDK_SETOP_UNION           rb + lb == 0   (the run's first row, whichever side: one row per distinct row)
+ *   HDK_SETOP_INTERSECT       left row, lb == 0, rb > 0
+ *   HDK_SETOP_INTERSECT_ALL   left row, lb < rb          (min(l, r) rows of a run with l left and r right rows)
+ *   HDK_SETOP_EXCEPT          left row, lb == 0, rb == 0
+ *   HDK_SETOP_EXCEPT_ALL      left row, lb >= rb         (max(l - r, 0) rows)
+ * Output: the kept rows in input order; output column j (of `num_outs`, 1..HDK_HIP_MAX_SETOP_OUTS) at
+ * out_cols + j * out_capacity holds their words of input column out_cols_idx[j] (any column: a subset of the keys, the tag).
+ * *row_count (device) ALWAYS receives the true number of kept rows; rows at or beyond out_capacity are not written, and
+ * nothing outside [0, min(kept, out_capacity)) of an output column is touched.  out_cols == NULL (or out_capacity == 0):
+ * count only.  The input is not modified, and no two of cols, out_cols, row_count and workspace may overlap (out_cols in a
+ * count-only call has no bytes and overlaps nothing).
+ * `workspace`: hdk_hip_setop_columns_workspace_bytes(num_rows) bytes of device memory, 8-byte aligned (host arithmetic only:
+ * per tile of 4 096 rows 512 bytes of keep bits -- one bit per row -- and 20 bytes of counters, plus at most 1.5 KiB), or
+ * NULL -- the library then takes it from the stream's memory pool (hipMallocAsync), as its siblings do.
+ * ASYNCHRONOUS on `stream`: six launches (summary, scan, carry scan, keep, scan, compact; five in a count-only call) ordered
+ * by the stream alone -- no atomics, no look-back; the host never waits.  Output and *row_count are complete when `stream`
+ * has drained.
+ * Errors, all found before any device is touched (HDK_HIP_ERR_INVALID_ARG with a message): a NULL cols / key_cols /
+ * out_cols_idx / row_count, num_cols < 1, num_keys outside 1..8, num_outs outside 1..16, an op outside hdk_hip_setop, a column
+ * index outside [0, num_cols), a tag_col that is a key, num_rows >= 2^32, num_rows > capacity, overlapping blocks, a
+ * workspace that is too small or not 8-byte aligned.
+ * num_rows == 0: *row_count = 0 is stored on the stream, nothing else is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define HDK_HIP_MAX_SETOP_COLUMNS 8 /* the limit of hdk_hip_sort_columns' entries and hdk_hip_group_columns' keys */
+#define HDK_HIP_MAX_SETOP_OUTS 16
+#define HDK_HIP_CONCAT_TAG_FIRST 1u /* flags: the side column holds 1 for the left block's rows and 0 for the right's */
+
+typedef enum hdk_hip_setop {
+  HDK_SETOP_UNION = 0,
+  HDK_SETOP_INTERSECT = 1,
+  HDK_SETOP_INTERSECT_ALL = 2,
+  HDK_SETOP_EXCEPT = 3,
+  HDK_SETOP_EXCEPT_ALL = 4
+} hdk_hip_setop;
+
+typedef struct hdk_hip_setop_col {
+  int32_t lcol;          /* column of the left block */
+  int32_t rcol;          /* column of the right block */
+  uint8_t lnullable;     /* 0: lnull_bits is an ordinary value */
+  uint8_t rnullable;
+  uint8_t pad_[6];
+  int64_t lnull_bits;    /* the left column's in-band NULL, as in hdk_hip_order_entry */
+  int64_t rnull_bits;
+  int64_t out_null_bits; /* what a NULL of either side is written as */
+} hdk_hip_setop_col;
+
+int32_t hdk_hip_concat_columns(const int64_t* lcols, uint64_t lcapacity, int32_t lnum_cols, uint64_t lnum_rows,
+                               const int64_t* rcols, uint64_t rcapacity, int32_t rnum_cols, uint64_t rnum_rows,
+                               const hdk_hip_setop_col* pairs, int32_t num_cols, int32_t side_col, uint32_t flags,
+                               int64_t* out_cols, uint64_t out_capacity, int32_t device_id, void* stream);
+size_t hdk_hip_setop_columns_workspace_bytes(uint64_t num_rows);
+int32_t hdk_hip_setop_columns(const int64_t* cols, uint64_t capacity, int32_t num_cols, uint64_t num_rows,
+                              const int32_t* key_cols, int32_t num_keys, int32_t tag_col, int32_t op,
+                              const int32_t* out_cols_idx, int32_t num_outs, int64_t* out_cols, uint64_t out_capacity,
+                              uint64_t* row_count, void* workspace, size_t workspace_bytes, int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Environment switches (MI355X addition; no reference counterpart: the reference's knobs are Config fields,
  * Shared/Config.h).  libhdk_hip.so reads its HDK_HIP_* variables (tests and A/B measurements, none needed
  * in production) ONCE per process, at the first launch that asks for one -- never per launch, so a host that calls
