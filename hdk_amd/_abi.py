@@ -31,6 +31,7 @@ JOIN_NULL_SAFE = 1  # hdk_hip_join_columns flags; its types are JOIN_INNER / JOI
 MAX_SETOP_COLUMNS = 8
 MAX_SETOP_OUTS = 16
 CONCAT_TAG_FIRST = 1  # hdk_hip_concat_columns flags
+MAX_CHUNK_COLUMNS = 16  # hdk_hip_chunk_columns
 SETOP_UNION, SETOP_INTERSECT, SETOP_INTERSECT_ALL, SETOP_EXCEPT, SETOP_EXCEPT_ALL = range(5)  # hdk_hip_setop
 JOIN_NO_ROW = 0xFFFFFFFF  # rperm_out of an output row without a partner
 SORT_NO_SELECT = 1  # hdk_hip_sort_columns flags
@@ -237,6 +238,19 @@ class SetopCol(C.Structure):
     out_null_bits."""
     _fields_ = [("lcol", C.c_int32), ("rcol", C.c_int32), ("lnullable", C.c_uint8), ("rnullable", C.c_uint8),
                 ("pad_", C.c_uint8 * 6), ("lnull_bits", C.c_int64), ("rnull_bits", C.c_int64), ("out_null_bits", C.c_int64)]
+
+
+class ChunkCol(C.Structure):
+    """hdk_hip_chunk_col: one selected column of hdk_hip_chunk_columns: input column `col`; a word of a nullable column that
+    equals null_bits is written as out_null_bits, the NULL of the 8-byte storage type."""
+    _fields_ = [("col", C.c_int32), ("is_fp", C.c_uint8), ("nullable", C.c_uint8), ("pad_", C.c_uint8 * 2),
+                ("null_bits", C.c_int64), ("out_null_bits", C.c_int64)]
+
+
+class ChunkStatsRecord(C.Structure):
+    """hdk_hip_chunk_stats: what hdk_hip_chunk_columns leaves per (column, fragment); min_bits / max_bits are meaningful
+    only when value_count > 0 (an fp fragment of NaNs only: min_bits = +inf, max_bits = -inf)."""
+    _fields_ = [("min_bits", C.c_int64), ("max_bits", C.c_int64), ("null_count", C.c_uint64), ("value_count", C.c_uint64)]
 
 
 class KernelOptions(C.Structure):

@@ -479,5 +479,7 @@ size_t hdk_hip_sizeof_project_out(void) { return sizeof(hdk_hip_project_out); }
 size_t hdk_hip_sizeof_join_key(void) { return sizeof(hdk_hip_join_key); }
 size_t hdk_hip_sizeof_join_out(void) { return sizeof(hdk_hip_join_out); }
 size_t hdk_hip_sizeof_setop_col(void) { return sizeof(hdk_hip_setop_col); }
+size_t hdk_hip_sizeof_chunk_col(void) { return sizeof(hdk_hip_chunk_col); }
+size_t hdk_hip_sizeof_chunk_stats(void) { return sizeof(hdk_hip_chunk_stats); }
 
 }  // extern "C"

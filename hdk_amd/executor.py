@@ -14,6 +14,7 @@ All compute goes through the C ABI; there is no CPU execution path in this packa
 """
 import ctypes as C
 import dataclasses
+import itertools
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -27,17 +28,34 @@ from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, GROUP_KINDS, JOIN_TYPE
                    CompiledPlan, Having, columnar_init_vals, compact_init_vals, compile_query, describe_columns, eff_key_count, has_count_distinct, regroup_columns,
                    group_windows, is_row_unit, resolve_having_columns, resolve_join_columns, resolve_order_by, resolve_select_columns,
                    resolve_setop_columns, resolve_window_columns, split_count_distinct, split_project_calls, split_row_unit)
-from .storage import ArrowStorage
+from .storage import (DEFAULT_FRAGMENT_SIZE, ArrowStorage, Column, DeviceTable, registered_column_type,
+                      stats_from_record)
+
+
+class DeviceView:
+    """A stretch of device memory that someone else owns: what BufferCache hands out for a storage.DeviceTable's chunks.
+    Reads like a DeviceBuffer; free() does nothing."""
+
+    def __init__(self, ptr: int, nbytes: int, device: int):
+        self.ptr, self.nbytes, self.device = ptr, nbytes, device
+
+    def free(self):
+        pass
 
 
 class BufferCache:
-    """Device-resident chunks, keyed like DataMgr's GPU_LEVEL chunk cache (table, column, fragment)."""
+    """Device-resident chunks, keyed like DataMgr's GPU_LEVEL chunk cache (table, column, fragment).  The chunks of a
+    storage.DeviceTable already are device-resident and belong to the table: chunk() / linearized() return a view of them
+    computed from the table at hand and store nothing, so clear() never frees a table's block and a name that is
+    registered again never serves the pointers of its predecessor."""
 
     def __init__(self, mgr: HipMgr, device_id: int):
         self.mgr, self.device_id = mgr, device_id
         self._chunks: Dict[tuple, DeviceBuffer] = {}
 
     def chunk(self, table, col_name, frag_idx) -> DeviceBuffer:
+        if isinstance(table, DeviceTable):
+            return DeviceView(table.device_chunk(col_name, frag_idx), table.frag_rows[frag_idx] * 8, table.device_id)
         key = (table.name, col_name, frag_idx)
         b = self._chunks.get(key)
         if b is None:
@@ -47,6 +65,8 @@ class BufferCache:
 
     def linearized(self, table, col_name) -> DeviceBuffer:
         """All fragments of an inner-join column as one buffer (ColumnFetcher::linearizeColumnFragments)."""
+        if isinstance(table, DeviceTable):  # (its columns are contiguous)
+            return DeviceView(table.device_column(col_name), table.num_rows * 8, table.device_id)
         key = (table.name, col_name, "all")
         b = self._chunks.get(key)
         if b is None:
@@ -991,7 +1011,109 @@ class Executor:
         self.init_projection_buffers = False  # see PreparedStep.init_output
 
     def compile(self, q: QueryUnit) -> CompiledPlan:
+        if isinstance(q.table, QueryUnit):
+            raise ValueError("a unit over a FROM-subquery has no plan before the inner unit has run: its layout is sized from "
+                             "the statistics of the inner result; execute() it")
         return compile_query(self.storage, q)
+
+    _subquery_ids = itertools.count()
+
+    def register_columns(self, name: str, cols: DeviceColumns, columns=None, fragment_size: Optional[int] = None) -> DeviceTable:
+        """Dense result columns as a table that the scan kernels read (hdk_hip_chunk_columns; the device form of
+        ArrowStorage's import: sentinel rewrite, ArrowStorageUtils.cpp:176-213, and computeStats) -> the storage.DeviceTable,
+        added to this executor's storage under `name`; `cols` stays valid and unmodified.  `columns` selects and orders the
+        columns by name or index (default: all of them, at most 16).  Every column becomes an 8-byte storage column of its
+        kind (storage.registered_column_type), its NULLs rewritten to that type's sentinel; the table owns one new block, a
+        copy: the chunks of a fresh block start on 256-byte boundaries, as every chunk the scan kernels have met.
+        `fragment_size` (default storage.DEFAULT_FRAGMENT_SIZE) is ROUNDED UP to a multiple of 32 for the same reason.
+        The per-fragment statistics are read back after one stream synchronisation.
+        A ValueError: duplicate or empty column names, cols.error_code != 0, freed columns, more than 16 columns, a column
+        without an 8-byte storage form (a boolean, a DATE in days: leave it out with columns=), a name that is a table
+        already.  The table can only be the OUTER table of a unit; drop_registered(name) frees it."""
+        if not isinstance(name, str) or not name:
+            raise ValueError("a registered table needs a name")
+        if name in self.storage.tables:
+            raise ValueError(f"{name!r} is already a table: drop it first")
+        if cols.error_code != 0:
+            raise ValueError(f"the columns carry error code {cols.error_code}: they are not a complete result")
+        if cols.device_id != self.device_id:
+            raise ValueError("the columns live on another device")
+        by_name = {d.name: i for i, d in enumerate(cols.schema)}
+        picked = []
+        for c in (range(cols.num_cols) if columns is None else columns):
+            if isinstance(c, str):
+                if c not in by_name:
+                    raise ValueError(f"columns= names no column: {c!r}")
+                picked.append(by_name[c])
+            elif isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < cols.num_cols:
+                raise ValueError(f"columns= index {c!r} outside 0..{cols.num_cols - 1}")
+            else:
+                picked.append(int(c))
+        if not 1 <= len(picked) <= A.MAX_CHUNK_COLUMNS:
+            raise ValueError(f"{len(picked)} columns: a registered table takes 1..{A.MAX_CHUNK_COLUMNS} (select with columns=)")
+        descs = [cols.schema[i] for i in picked]
+        names = [d.name for d in descs]
+        if any(not n for n in names) or len(set(names)) != len(names):
+            raise ValueError(f"the column names {names} are empty or not unique: a table's columns are found by name")
+        types = [registered_column_type(d) for d in descs]
+        fragment_rows = int(fragment_size or DEFAULT_FRAGMENT_SIZE)
+        if fragment_rows <= 0:
+            raise ValueError("fragment_size must be positive")
+        fragment_rows = (fragment_rows + 31) // 32 * 32
+        n, nc = cols.num_rows, len(picked)
+        src = cols._block_ptr() if n else None
+        nfrag = max(1, -(-n // fragment_rows))
+        out_capacity = max((n + 31) // 32 * 32, 32)
+        sel = (A.ChunkCol * nc)()
+        for j, (i, d, t) in enumerate(zip(picked, descs, types)):
+            sel[j] = A.ChunkCol(i, int(d.is_fp), int(d.nullable), (C.c_uint8 * 2)(), A.to_i64(d.null_bits), A.to_i64(t.null_value()))
+        block = self.mgr.alloc(nc * out_capacity * 8, self.device_id)
+        try:
+            d_stats = self.mgr.alloc(nc * nfrag * C.sizeof(A.ChunkStatsRecord), self.device_id)
+            try:
+                check(lib().hdk_hip_chunk_columns(src, cols.capacity if n else 0, cols.num_cols, n, sel, nc, fragment_rows,
+                                                  block.ptr, out_capacity, d_stats.ptr, None, 0, self.device_id, None))
+                self.mgr.synchronizeStream(self.device_id)
+                rec = self.mgr.to_host(d_stats.ptr, nc * nfrag * 32, self.device_id, np.int64).reshape(nc, nfrag, 4)
+            finally:
+                d_stats.free()
+            frag_rows = [min(fragment_rows, n - b) for b in range(0, n, fragment_rows)] or [0]
+            table_cols = []
+            for j, (d, t) in enumerate(zip(descs, types)):
+                stats = [stats_from_record(t, int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in rec[j]]
+                table_cols.append(Column(d.name, t, [], stats, d.dictionary))
+            table = DeviceTable(name, table_cols, frag_rows, block, out_capacity, fragment_rows, self.device_id)
+        except Exception:
+            block.free()
+            raise
+        return self.storage.add_table(table)
+
+    def drop_registered(self, name: str):
+        """Remove a table that register_columns made and free its block."""
+        t = self.storage.tables.get(name)
+        if not isinstance(t, DeviceTable):
+            raise ValueError(f"{name!r} is not a registered result")
+        self.storage.drop_table(name)
+        t.free()
+
+    def _execute_subquery(self, q: QueryUnit, device_type, frag_ids, result, **kw):
+        """A unit whose `table` is a QueryUnit (a FROM-subquery): the inner unit runs with result="columns", all its stages
+        included; its columns are registered under a private name and handed back; the outer unit runs over that table like
+        over any other, and the table is dropped -- also when a step raises.  An inner unit may itself read a subquery."""
+        cols = self.execute(q.table, device_type, None, "columns")
+        name = None
+        try:
+            try:
+                name = "__subquery_%d" % next(self._subquery_ids)
+                while name in self.storage.tables:
+                    name = "__subquery_%d" % next(self._subquery_ids)
+                self.register_columns(name, cols)
+            finally:
+                cols.free()
+            return self.execute(dataclasses.replace(q, table=name), device_type, frag_ids, result, **kw)
+        finally:
+            if name is not None and isinstance(self.storage.tables.get(name), DeviceTable):
+                self.drop_registered(name)
 
     def _join_columns(self, inner, info):
         """JoinColumn / JoinColumnTypeInfo per key column: one JoinChunk per inner fragment."""
@@ -1116,13 +1238,16 @@ class Executor:
 
     def execute(self, q: QueryUnit, device_type: str = "GPU", frag_ids=None, result: str = "buffer", **kw):
         """-> ExecutionResult (the host copy of the buffer), or with result="columns" a DeviceColumns: the step's dense
-        columns in device memory (PreparedStep.fetch_columns).  On a projection or a non-grouped QueryUnit, result_joins,
+        columns in device memory (PreparedStep.fetch_columns).  `q.table` may be a QueryUnit, a FROM-subquery
+        (_execute_subquery): its result never leaves the device.  On a projection or a non-grouped QueryUnit, result_joins,
         result_setops, windows, select and the SortInfo are taken off the unit (plan.split_row_unit) and applied to its columns."""
         if device_type != "GPU":
             raise QueryMustRunOnCpu("hdk_amd ships the GPU path only; run device_type='CPU' on HDK itself")
         if result not in ("buffer", "columns"):
             raise ValueError(f"result must be 'buffer' or 'columns', not {result!r}")
         sq = q.query if isinstance(q, CompiledPlan) else q
+        if isinstance(q, QueryUnit) and isinstance(q.table, QueryUnit):
+            return self._execute_subquery(q, device_type, frag_ids, result, **kw)
         # a projection or a non-grouped unit: what compile_query refuses on it is applied to its dense columns below
         row_unit = isinstance(q, QueryUnit) and is_row_unit(q)
         if sq.result_setops and result == "buffer":

@@ -352,4 +352,26 @@ inline void setop_columns_on_device(const int64_t* cols, const size_t capacity, 
                               workspace, workspace_bytes, device_id, nullptr));
 }
 
+// A result that sits in HBM as the input of the next step's SCAN: the device form of what ArrowStorage does on import -- the
+// sentinel rewrite (ArrowStorage/ArrowStorageUtils.cpp:176-213) and the chunk metadata (ArrowStorage's computeStats).
+// chunk_columns_on_device copies the selected dense columns into `out_cols` (a fresh, 256-byte-aligned block: column j at
+// out_cols + j * out_capacity, fragment f of it fragment_rows * f rows further on), writes each nullable column's in-band
+// NULL as sel[j].out_null_bits -- the NULL of the 8-byte storage type -- and leaves one hdk_hip_chunk_stats per (column,
+// fragment) in `stats_dev` (device, [num_cols][max(1, ceil(num_rows / fragment_rows))]): min / max / null_count /
+// value_count, from which ChunkMetadata is filled once the stream has drained.  fragment_rows and (with more than one
+// column) out_capacity are multiples of 32.  `workspace` comes from the BufferProvider
+// (chunk_columns_workspace_bytes(num_rows, fragment_rows, num_cols) bytes) or is null (the stream's memory pool).
+// Asynchronous on the device's stream: the host never waits.
+inline size_t chunk_columns_workspace_bytes(const size_t num_rows, const size_t fragment_rows, const int num_cols) {
+  return hdk_hip_chunk_columns_workspace_bytes(static_cast<uint64_t>(num_rows), static_cast<uint64_t>(fragment_rows), num_cols);
+}
+inline void chunk_columns_on_device(const int64_t* cols, const size_t capacity, const int num_cols_in, const size_t num_rows,
+                                    const hdk_hip_chunk_col* sel, const int num_cols, const size_t fragment_rows,
+                                    int64_t* out_cols, const size_t out_capacity, hdk_hip_chunk_stats* stats_dev,
+                                    int8_t* workspace, const size_t workspace_bytes, const int device_id) {
+  check(hdk_hip_chunk_columns(cols, static_cast<uint64_t>(capacity), num_cols_in, static_cast<uint64_t>(num_rows), sel, num_cols,
+                              static_cast<uint64_t>(fragment_rows), out_cols, static_cast<uint64_t>(out_capacity), stats_dev,
+                              workspace, workspace_bytes, device_id, nullptr));
+}
+
 }  // namespace hip_rt

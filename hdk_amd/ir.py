@@ -301,8 +301,10 @@ class ResultSetOp:
 
 @dataclass
 class QueryUnit:
-    """What one execution step needs (cf. RelAlgExecutionUnit)."""
-    table: str
+    """What one execution step needs (cf. RelAlgExecutionUnit).  `table` names a table of the storage, or is itself a
+    QueryUnit -- a FROM-subquery, which Executor.execute runs first and scans where it lies, in device memory (a registered
+    result can only be the outer table; Executor.compile refuses such a unit: its plan needs the inner result's statistics)."""
+    table: Union[str, "QueryUnit"]
     quals: List[Cond] = field(default_factory=list)  # conjunction of conditions (each a Cmp or an And / Or / Not tree)
     joins: List[JoinSpec] = field(default_factory=list)
     groupby: List[Expr] = field(default_factory=list)

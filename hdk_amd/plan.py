@@ -21,7 +21,7 @@ import numpy as np
 from . import _abi as A
 from .ir import (Agg, And, BinOp, Cast, Cmp, ColRef, Expr, ExtractYear, KeyRef, Lit, Not, Or, QueryMustRunOnCpu,
                  QueryUnit, TargetRef, Type, Window, WINDOW_FRAMES, WINDOW_KINDS)
-from .storage import ArrowStorage, Table
+from .storage import ArrowStorage, DeviceTable, Table
 
 BASELINE_THRESHOLD = 1_000_000  # Config.exec.group_by.baseline_threshold (Shared/Config.h:51)
 DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS = 16384  # Shared/Config.h:42
@@ -1072,6 +1072,9 @@ def _compile_joins_and_quals(b: "_Binder", q: QueryUnit, p: A.Plan):
     p.num_joins = len(q.joins)
     for ji, j in enumerate(q.joins):
         inner = b.inner[ji]
+        if isinstance(inner, DeviceTable):
+            # (the one-to-one / matching-set decision, _inner_keys_unique, reads host fragments)
+            raise QueryMustRunOnCpu("a registered result can only be scanned as the outer table")
         okeys, icols = j.outer_keys, j.inner_cols
         if len(okeys) != len(icols) or not 1 <= len(okeys) <= A.MAX_JOIN_KEYS:
             raise QueryMustRunOnCpu("join key lists must have 1..%d matching entries" % A.MAX_JOIN_KEYS)

@@ -8,7 +8,9 @@ Mirrors the part of the reference the kernels depend on (omniscidb/ArrowStorage/
     int32 ids (StringDictionary is out of scope: ids come from Arrow's own dictionary);
   * per-fragment chunk metadata (min / max / has_nulls) as ArrowStorage computes it
     (ArrowStorage.cpp computeStats) -- the inputs of ColRangeInfo / ExpressionRange.
-Host buffers are numpy arrays; device residency is the executor's buffer cache.
+Host buffers are numpy arrays; device residency is the executor's buffer cache.  A `DeviceTable` is the exception: a
+result that already sits in device memory, registered as a table (Executor.register_columns); its chunks were never on
+the host and its statistics come from the device (hdk_hip_chunk_columns).
 """
 from dataclasses import dataclass
 from typing import Dict, List, Optional
@@ -57,6 +59,74 @@ class Table:
     @property
     def num_fragments(self):
         return len(self.frag_rows)
+
+
+class DeviceTable(Table):
+    """A table whose chunks live in ONE device block and nowhere else: what Executor.register_columns makes of dense result
+    columns (hdk_hip_chunk_columns).  Column j of the block starts at block + j * out_capacity * 8 and is contiguous;
+    fragment f of it starts fragment_rows * f rows further on, on a 256-byte boundary.  Every column is 8 bytes wide;
+    `Column.fragments` are empty and `Column.stats` come from the device.  Owns the block until free(): the executor's
+    buffer cache hands out views of it and never stores or frees them.  It can only be the OUTER table of a unit: the
+    planner's one-to-one decision for an inner table reads host fragments."""
+
+    def __init__(self, name, columns: List[Column], frag_rows: List[int], block, out_capacity: int, fragment_rows: int,
+                 device_id: int = 0):
+        super().__init__(name, columns, frag_rows)
+        self.block, self.out_capacity, self.fragment_rows, self.device_id = block, int(out_capacity), int(fragment_rows), device_id
+
+    def _base(self) -> int:
+        if self.block is None or not self.block.ptr:
+            raise ValueError(f"the registered table {self.name!r} has been freed")
+        return int(self.block.ptr)
+
+    def device_column(self, col_name) -> int:
+        """Device address of the whole column: num_rows 8-byte words"""
+        return self._base() + self.column_order.index(col_name) * self.out_capacity * 8
+
+    def device_chunk(self, col_name, frag_idx: int) -> int:
+        """Device address of fragment `frag_idx` of the column: frag_rows[frag_idx] 8-byte words"""
+        if not 0 <= frag_idx < self.num_fragments:
+            raise IndexError(frag_idx)
+        return self.device_column(col_name) + frag_idx * self.fragment_rows * 8
+
+    def free(self):
+        if self.block is not None:
+            self.block.free()
+            self.block = None
+
+
+REGISTERED_KINDS = ("int", "decimal", "timestamp", "date", "fp", "dict")
+
+
+def registered_column_type(desc) -> Type:
+    """The 8-byte storage type of a dense result column (a plan.ColumnDesc) registered as a table column: the column's kind
+    at 8 bytes, nullable as the column is, a decimal's scale and a timestamp's unit kept; COUNT is a plain integer.  A
+    dictionary-encoded column keeps its kind (the dictionary travels in Column.dictionary).  A ValueError for what has no
+    8-byte storage form here: a boolean and a DATE in days."""
+    t = desc.type
+    if desc.is_fp:
+        return Type("fp", 8, bool(desc.nullable))
+    if desc.agg == "count":
+        return Type("int", 8, bool(desc.nullable))
+    if t.kind not in REGISTERED_KINDS or t.is_fp or t.is_date_in_days:
+        what = "a DATE in days" if t.is_date_in_days else f"kind {t.kind!r}"
+        raise ValueError(f"column {desc.name!r} ({what}) has no 8-byte storage form: leave it out with columns=")
+    scale = (t.scale or desc.scale) if t.kind == "decimal" else 0
+    return Type(t.kind, 8, bool(desc.nullable), scale, t.unit)
+
+
+def stats_from_record(t: Type, min_bits: int, max_bits: int, null_count: int, value_count: int) -> ChunkStats:
+    """ChunkStats of one (column, fragment) from its hdk_hip_chunk_stats record: what _stats gives for the same words on the
+    host.  min / max are None when no value took part: no non-NULL word, or NaNs only (the record then holds +inf / -inf)."""
+    has_nulls = null_count > 0
+    if value_count == 0:
+        return ChunkStats(None, None, has_nulls)
+    if t.is_fp:
+        lo, hi = (float(x) for x in np.array([min_bits, max_bits], dtype=np.int64).view(np.float64))
+        if lo > hi:
+            return ChunkStats(None, None, has_nulls)
+        return ChunkStats(lo, hi, has_nulls)
+    return ChunkStats(int(min_bits), int(max_bits), has_nulls)
 
 
 _NP_OF = {1: np.int8, 2: np.int16, 4: np.int32, 8: np.int64}

@@ -1162,6 +1162,71 @@ int32_t hdk_hip_setop_columns(const int64_t* cols, uint64_t capacity, int32_t nu
                               uint64_t* row_count, void* workspace, size_t workspace_bytes, int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dense result columns as the chunks of a table: the copy, the sentinel rewrite and the chunk statistics that make a
+ * device result the INPUT of a scan step.
+ * The device form, for a result whose columns sit in HBM, of what ArrowStorage does when a table is imported: null values
+ * rewritten to the column type's in-band sentinel (omniscidb/ArrowStorage/ArrowStorageUtils.cpp:176-213) and the
+ * per-fragment chunk metadata min / max / has_nulls (ArrowStorage's computeStats) from which the planner sizes every layout
+ * (ColRangeInfo, ExpressionRange).
+ *
+ * Input: `num_cols_in` dense columns of `num_rows` 8-byte words, column t at cols + t * capacity, NULLs in band -- what the
+ * other *_columns calls write.  `sel`: `num_cols` (1..HDK_HIP_MAX_CHUNK_COLUMNS) selected columns, in output order; a column
+ * may be selected more than once.
+ * Copy: output column j at out_cols + j * out_capacity holds rows [0, num_rows) of input column sel[j].col.  A word of a
+ * nullable column that EQUALS null_bits (a bit compare) is written as out_null_bits; every other word is written unchanged --
+ * so a non-NULL word that equals out_null_bits reads as NULL afterwards, the in-band rule of every *_columns call.  A word of
+ * a column that is not nullable is never rewritten and never counted as NULL.  Nothing outside rows [0, num_rows) of an
+ * output column is touched; the input is not modified.
+ * The output is a COPY by design: input column t starts at an address that is only 8-byte aligned, while the scan kernels
+ * read chunks that start on 256-byte boundaries.  With out_cols 256-byte aligned, fragment_rows % 32 == 0 and
+ * out_capacity % 32 == 0 every chunk out_cols + j * out_capacity + f * fragment_rows is.
+ * Statistics: num_fragments = max(1, ceil(num_rows / fragment_rows)); fragment f of a column is rows
+ * [f * fragment_rows, min((f + 1) * fragment_rows, num_rows)).  stats[j * num_fragments + f] (device) receives, over the
+ * OUTPUT words of that fragment: null_count -- the words of a nullable column that equal out_null_bits, i.e. what reads as
+ * NULL afterwards --, value_count -- all other words --, and the min and max of those other words: compared as signed int64,
+ * or for an is_fp column compared as doubles with the BIT PATTERN of the winning value stored.  An fp word that is a NaN is not
+ * NULL and counts in value_count but takes no part in min / max -- a deviation from numpy's min(), which propagates a NaN.
+ * -0.0 and +0.0 compare equal; either may be stored.  min_bits / max_bits are meaningful only when value_count > 0; an fp
+ * fragment whose values are all NaN leaves min_bits = +inf and max_bits = -inf (min > max: no value took part).
+ * `workspace`: hdk_hip_chunk_columns_workspace_bytes(num_rows, fragment_rows, num_cols) bytes of device memory, 8-byte aligned
+ * (host arithmetic only: one 32-byte partial per column and tile of 4 096 rows, tiles cut at fragment boundaries -- every
+ * fragment but the last has ceil(fragment_rows / 4 096) tiles, the last those of its own rows -- rounded up to 256 bytes), or
+ * NULL -- the library then takes it from the stream's memory pool (hipMallocAsync), as its siblings do.
+ * ASYNCHRONOUS on `stream`: two launches (the streaming copy that leaves the partials, the fold per column and fragment)
+ * ordered by the stream alone -- no atomics, no look-back; the host never waits.  Output and stats are complete when
+ * `stream` has drained.
+ * Errors, all found before any device is touched (HDK_HIP_ERR_INVALID_ARG with a message): a NULL sel / out_cols / stats
+ * (cols with rows), num_cols outside 1..16, a column index outside [0, num_cols_in), fragment_rows 0 or not a multiple of
+ * 32, num_rows >= 2^32, num_rows > capacity or > out_capacity, out_capacity not a multiple of 32 when num_cols > 1, out_cols
+ * overlapping cols (or any two of cols, out_cols, stats and workspace overlapping), a workspace that is too small or not
+ * 8-byte aligned.
+ * num_rows == 0: one all-zero stats record per column is stored on the stream, nothing else is launched.
+ * ---------------------------------------------------------------------------------------- */
+#define HDK_HIP_MAX_CHUNK_COLUMNS 16
+
+typedef struct hdk_hip_chunk_col {
+  int32_t col;           /* column of the input block */
+  uint8_t is_fp;         /* min / max compare the words as doubles */
+  uint8_t nullable;      /* 0: null_bits is an ordinary value */
+  uint8_t pad_[2];
+  int64_t null_bits;     /* the input column's in-band NULL, as in hdk_hip_order_entry */
+  int64_t out_null_bits; /* what a NULL is written as: the NULL of the 8-byte storage type */
+} hdk_hip_chunk_col;
+
+typedef struct hdk_hip_chunk_stats {
+  int64_t min_bits;
+  int64_t max_bits;
+  uint64_t null_count;
+  uint64_t value_count;
+} hdk_hip_chunk_stats;
+
+size_t hdk_hip_chunk_columns_workspace_bytes(uint64_t num_rows, uint64_t fragment_rows, int32_t num_cols);
+int32_t hdk_hip_chunk_columns(const int64_t* cols, uint64_t capacity, int32_t num_cols_in, uint64_t num_rows,
+                              const hdk_hip_chunk_col* sel, int32_t num_cols, uint64_t fragment_rows, int64_t* out_cols,
+                              uint64_t out_capacity, hdk_hip_chunk_stats* stats, void* workspace, size_t workspace_bytes,
+                              int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Environment switches (MI355X addition; no reference counterpart: the reference's knobs are Config fields,
  * Shared/Config.h).  libhdk_hip.so reads its HDK_HIP_* variables (tests and A/B measurements, none needed
  * in production) ONCE per process, at the first launch that asks for one -- never per launch, so a host that calls
