@@ -32,6 +32,7 @@ MAX_SETOP_COLUMNS = 8
 MAX_SETOP_OUTS = 16
 CONCAT_TAG_FIRST = 1  # hdk_hip_concat_columns flags
 MAX_CHUNK_COLUMNS = 16  # hdk_hip_chunk_columns
+KEYS_NULLS_MATCH = 1  # hdk_hip_key_multiplicity flags
 SETOP_UNION, SETOP_INTERSECT, SETOP_INTERSECT_ALL, SETOP_EXCEPT, SETOP_EXCEPT_ALL = range(5)  # hdk_hip_setop
 JOIN_NO_ROW = 0xFFFFFFFF  # rperm_out of an output row without a partner
 SORT_NO_SELECT = 1  # hdk_hip_sort_columns flags
@@ -251,6 +252,19 @@ class ChunkStatsRecord(C.Structure):
     """hdk_hip_chunk_stats: what hdk_hip_chunk_columns leaves per (column, fragment); min_bits / max_bits are meaningful
     only when value_count > 0 (an fp fragment of NaNs only: min_bits = +inf, max_bits = -inf)."""
     _fields_ = [("min_bits", C.c_int64), ("max_bits", C.c_int64), ("null_count", C.c_uint64), ("value_count", C.c_uint64)]
+
+
+class MultiplicityKey(C.Structure):
+    """hdk_hip_multiplicity_key: one key column of hdk_hip_key_multiplicity; min_val / max_val / translated_null are the
+    JoinColumnTypeInfo of the perfect table (read on the perfect route only)."""
+    _fields_ = [("col", C.c_int32), ("nullable", C.c_uint8), ("pad_", C.c_uint8 * 3), ("null_bits", C.c_int64),
+                ("min_val", C.c_int64), ("max_val", C.c_int64), ("translated_null", C.c_int64)]
+
+
+class KeyMultiplicityResult(C.Structure):
+    """hdk_hip_key_multiplicity_result: the record hdk_hip_key_multiplicity leaves."""
+    _fields_ = [("max_matches", C.c_uint64), ("occupied", C.c_uint64), ("rows_filed", C.c_uint64),
+                ("rows_out_of_range", C.c_uint64)]
 
 
 class KernelOptions(C.Structure):

@@ -99,6 +99,9 @@ SIGNATURES = {
     "hdk_hip_chunk_columns_workspace_bytes": (sz, [C.c_uint64, C.c_uint64, i32]),
     "hdk_hip_chunk_columns": (i32, [v, C.c_uint64, i32, C.c_uint64, C.POINTER(A.ChunkCol), i32, C.c_uint64, v, C.c_uint64, v, v,
                                     sz, i32, v]),
+    "hdk_hip_key_multiplicity_workspace_bytes": (sz, [C.c_uint64, C.POINTER(A.MultiplicityKey), i32, C.c_int64]),
+    "hdk_hip_key_multiplicity": (i32, [v, C.c_uint64, i32, C.c_uint64, C.POINTER(A.MultiplicityKey), i32, C.c_int64, C.c_int64, u32,
+                                       v, v, sz, i32, v]),
     "hdk_hip_exchange_shape_for": (i32, [C.POINTER(A.Plan), C.POINTER(A.KernelOptions), i32, u32, i32,
                                          C.POINTER(A.ExchangeShape)]),
     "hdk_hip_scatter_to_owners": (i32, [C.POINTER(A.Plan), C.POINTER(v), C.POINTER(A.KernelOptions),
@@ -141,6 +144,8 @@ EXTRA_SIGNATURES = {
     "hdk_hip_sizeof_setop_col": (sz, []),
     "hdk_hip_sizeof_chunk_col": (sz, []),
     "hdk_hip_sizeof_chunk_stats": (sz, []),
+    "hdk_hip_sizeof_multiplicity_key": (sz, []),
+    "hdk_hip_sizeof_key_multiplicity_result": (sz, []),
 }
 
 

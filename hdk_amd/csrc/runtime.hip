@@ -481,5 +481,7 @@ size_t hdk_hip_sizeof_join_out(void) { return sizeof(hdk_hip_join_out); }
 size_t hdk_hip_sizeof_setop_col(void) { return sizeof(hdk_hip_setop_col); }
 size_t hdk_hip_sizeof_chunk_col(void) { return sizeof(hdk_hip_chunk_col); }
 size_t hdk_hip_sizeof_chunk_stats(void) { return sizeof(hdk_hip_chunk_stats); }
+size_t hdk_hip_sizeof_multiplicity_key(void) { return sizeof(hdk_hip_multiplicity_key); }
+size_t hdk_hip_sizeof_key_multiplicity_result(void) { return sizeof(hdk_hip_key_multiplicity_result); }
 
 }  // extern "C"

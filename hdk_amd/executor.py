@@ -26,7 +26,7 @@ from .hip_mgr import DeviceBuffer, HipMgr
 from .ir import QueryMustRunOnCpu, QueryUnit, Type
 from .plan import (DEFAULT_MAX_GROUPS_BUFFER_ENTRY_GUESS, GROUP_KINDS, JOIN_TYPES, SETOP_CODES, SETOP_NAMES, ColumnDesc,
                    CompiledPlan, Having, columnar_init_vals, compact_init_vals, compile_query, describe_columns, eff_key_count, has_count_distinct, regroup_columns,
-                   group_windows, is_row_unit, resolve_having_columns, resolve_join_columns, resolve_order_by, resolve_select_columns,
+                   group_windows, is_row_unit, join_key_shape, resolve_having_columns, resolve_join_columns, resolve_order_by, resolve_select_columns,
                    resolve_setop_columns, resolve_window_columns, split_count_distinct, split_project_calls, split_row_unit)
 from .storage import (DEFAULT_FRAGMENT_SIZE, ArrowStorage, Column, DeviceTable, registered_column_type,
                       stats_from_record)
@@ -1011,14 +1011,65 @@ class Executor:
         self.init_projection_buffers = False  # see PreparedStep.init_output
 
     def compile(self, q: QueryUnit) -> CompiledPlan:
-        if isinstance(q.table, QueryUnit):
+        """plan.compile_query, after the device has been asked what the planner cannot read from the host: the key
+        multiplicity of every join whose inner table is a registered result (_measure_inner_tables)."""
+        if isinstance(q.table, QueryUnit) or any(isinstance(j.inner_table, QueryUnit) for j in q.joins):
             raise ValueError("a unit over a FROM-subquery has no plan before the inner unit has run: its layout is sized from "
                              "the statistics of the inner result; execute() it")
+        self._measure_inner_tables(q)
         return compile_query(self.storage, q)
+
+    def _measure_inner_tables(self, q: QueryUnit):
+        """For each join of `q` whose inner table is a joinable storage.DeviceTable and whose key is not yet in its key_multiplicity:
+        one hdk_hip_key_multiplicity call on the table's block, the 32-byte record read back and kept.  A semi or anti
+        join needs no number (the first row of a key wins the fill); a join that compile_query will refuse anyway (key
+        lists, key types, an inner table without a key value) is left to it."""
+        for j in q.joins:
+            inner = self.storage.tables.get(j.inner_table) if isinstance(j.inner_table, str) else None
+            if not isinstance(inner, DeviceTable) or not inner.joinable or j.type in ("semi", "anti"):
+                continue
+            icols = j.inner_cols
+            if len(j.outer_keys) != len(icols) or not 1 <= len(icols) <= A.MAX_JOIN_KEYS or \
+                    any(c not in inner.columns or not inner.columns[c].type.is_integer_like for c in icols):
+                continue
+            shape = join_key_shape(inner, j)
+            if shape is None or shape.multiplicity_key in inner.key_multiplicity:
+                continue
+            inner.key_multiplicity[shape.multiplicity_key] = self._key_multiplicity(inner, shape)
+
+    def _key_multiplicity(self, inner: DeviceTable, shape) -> tuple:
+        """-> (max_matches, occupied) of the join key `shape` (a plan.JoinKeyShape) over the rows of `inner`, filed as the
+        build of that join will file them.  A row outside the range the statistics give -- the build's -2, found before
+        anything is built -- raises QueryMustRunOnCpu."""
+        nk = len(shape.cols)
+        keys = (A.MultiplicityKey * nk)()
+        for i, c in enumerate(shape.cols):
+            col = inner.columns[c]
+            st = col.table_stats()
+            mn, mx = (int(st.min), int(st.max)) if st.min is not None else (0, 0)
+            # (nullable whatever the type says: the builds test every word against the type's NULL, JoinColumnTypeInfo)
+            keys[i] = A.MultiplicityKey(inner.column_order.index(c), 1, (C.c_uint8 * 3)(), A.to_i64(col.type.null_value()),
+                                        A.to_i64(mn), A.to_i64(mx), A.to_i64(mx + 1))
+        flags = A.KEYS_NULLS_MATCH if shape.nulls_match else 0
+        d_rec = self.mgr.alloc(C.sizeof(A.KeyMultiplicityResult), self.device_id)
+        try:
+            check(lib().hdk_hip_key_multiplicity(inner._base(), inner.out_capacity, len(inner.column_order), inner.num_rows, keys,
+                                                 nk, shape.entry_count, shape.bucket, flags, d_rec.ptr, None, 0, self.device_id,
+                                                 None))
+            self.mgr.synchronizeStream(self.device_id)
+            rec = self.mgr.to_host(d_rec.ptr, C.sizeof(A.KeyMultiplicityResult), self.device_id, np.uint64)
+        finally:
+            d_rec.free()
+        max_matches, occupied, _, outside = (int(x) for x in rec)
+        if outside:
+            raise QueryMustRunOnCpu(f"stale statistics: {outside} rows of the registered result {inner.name!r} hold a join key "
+                                    f"outside the range [{shape.min_key}, {shape.max_key}] its table would be sized from")
+        return max_matches, occupied
 
     _subquery_ids = itertools.count()
 
-    def register_columns(self, name: str, cols: DeviceColumns, columns=None, fragment_size: Optional[int] = None) -> DeviceTable:
+    def register_columns(self, name: str, cols: DeviceColumns, columns=None, fragment_size: Optional[int] = None,
+                         joinable: bool = False) -> DeviceTable:
         """Dense result columns as a table that the scan kernels read (hdk_hip_chunk_columns; the device form of
         ArrowStorage's import: sentinel rewrite, ArrowStorageUtils.cpp:176-213, and computeStats) -> the storage.DeviceTable,
         added to this executor's storage under `name`; `cols` stays valid and unmodified.  `columns` selects and orders the
@@ -1029,7 +1080,9 @@ class Executor:
         The per-fragment statistics are read back after one stream synchronisation.
         A ValueError: duplicate or empty column names, cols.error_code != 0, freed columns, more than 16 columns, a column
         without an 8-byte storage form (a boolean, a DATE in days: leave it out with columns=), a name that is a table
-        already.  The table can only be the OUTER table of a unit; drop_registered(name) frees it."""
+        already.  The table is the outer table of a unit; with joinable=True it may also be the INNER table of a join, whose
+        key multiplicity compile() then measures on the device (storage.DeviceTable.key_multiplicity) -- without it a join
+        against the table keeps the refusal it always got.  drop_registered(name) frees it."""
         if not isinstance(name, str) or not name:
             raise ValueError("a registered table needs a name")
         if name in self.storage.tables:
@@ -1082,35 +1135,48 @@ class Executor:
             for j, (d, t) in enumerate(zip(descs, types)):
                 stats = [stats_from_record(t, int(r[0]), int(r[1]), int(r[2]), int(r[3])) for r in rec[j]]
                 table_cols.append(Column(d.name, t, [], stats, d.dictionary))
-            table = DeviceTable(name, table_cols, frag_rows, block, out_capacity, fragment_rows, self.device_id)
+            table = DeviceTable(name, table_cols, frag_rows, block, out_capacity, fragment_rows, self.device_id, joinable)
         except Exception:
             block.free()
             raise
         return self.storage.add_table(table)
 
     def drop_registered(self, name: str):
-        """Remove a table that register_columns made and free its block."""
+        """Remove a table that register_columns made and free its block, and with it every join table and fused join table
+        built over it: both caches are keyed by the table's NAME, and a name registered again must not be served the hash
+        table of its predecessor."""
         t = self.storage.tables.get(name)
         if not isinstance(t, DeviceTable):
             raise ValueError(f"{name!r} is not a registered result")
         self.storage.drop_table(name)
+        for cache in (self._join_cache, self._fused_cache):
+            for key in [k for k in cache if k[0] == name]:
+                cache.pop(key).free()
         t.free()
 
     def _execute_subquery(self, q: QueryUnit, device_type, frag_ids, result, **kw):
-        """A unit whose `table` is a QueryUnit (a FROM-subquery): the inner unit runs with result="columns", all its stages
-        included; its columns are registered under a private name and handed back; the outer unit runs over that table like
-        over any other, and the table is dropped -- also when a step raises.  An inner unit may itself read a subquery."""
-        cols = self.execute(q.table, device_type, None, "columns")
+        """A unit that reads a QueryUnit -- as its `table` (a FROM-subquery) or as the inner table of a join --: that unit
+        runs with result="columns", all its stages included; its columns are registered under a private name and handed
+        back; the unit above runs over that table like over any other, and the table is dropped -- also when a step raises.
+        One subquery per call: the unit above comes back through execute() with the others.  An inner unit may itself
+        read a subquery."""
+        ji = next((i for i, j in enumerate(q.joins) if isinstance(j.inner_table, QueryUnit)), None)
+        cols = self.execute(q.table if ji is None else q.joins[ji].inner_table, device_type, None, "columns")
         name = None
         try:
             try:
                 name = "__subquery_%d" % next(self._subquery_ids)
                 while name in self.storage.tables:
                     name = "__subquery_%d" % next(self._subquery_ids)
-                self.register_columns(name, cols)
+                self.register_columns(name, cols, joinable=ji is not None)
             finally:
                 cols.free()
-            return self.execute(dataclasses.replace(q, table=name), device_type, frag_ids, result, **kw)
+            if ji is None:
+                above = dataclasses.replace(q, table=name)
+            else:
+                above = dataclasses.replace(q, joins=[dataclasses.replace(j, inner_table=name) if i == ji else j
+                                                      for i, j in enumerate(q.joins)])
+            return self.execute(above, device_type, frag_ids, result, **kw)
         finally:
             if name is not None and isinstance(self.storage.tables.get(name), DeviceTable):
                 self.drop_registered(name)
@@ -1238,15 +1304,15 @@ class Executor:
 
     def execute(self, q: QueryUnit, device_type: str = "GPU", frag_ids=None, result: str = "buffer", **kw):
         """-> ExecutionResult (the host copy of the buffer), or with result="columns" a DeviceColumns: the step's dense
-        columns in device memory (PreparedStep.fetch_columns).  `q.table` may be a QueryUnit, a FROM-subquery
-        (_execute_subquery): its result never leaves the device.  On a projection or a non-grouped QueryUnit, result_joins,
+        columns in device memory (PreparedStep.fetch_columns).  `q.table` and a join's `inner_table` may be a QueryUnit, a
+        subquery (_execute_subquery): its result never leaves the device.  On a projection or a non-grouped QueryUnit, result_joins,
         result_setops, windows, select and the SortInfo are taken off the unit (plan.split_row_unit) and applied to its columns."""
         if device_type != "GPU":
             raise QueryMustRunOnCpu("hdk_amd ships the GPU path only; run device_type='CPU' on HDK itself")
         if result not in ("buffer", "columns"):
             raise ValueError(f"result must be 'buffer' or 'columns', not {result!r}")
         sq = q.query if isinstance(q, CompiledPlan) else q
-        if isinstance(q, QueryUnit) and isinstance(q.table, QueryUnit):
+        if isinstance(q, QueryUnit) and (isinstance(q.table, QueryUnit) or any(isinstance(j.inner_table, QueryUnit) for j in q.joins)):
             return self._execute_subquery(q, device_type, frag_ids, result, **kw)
         # a projection or a non-grouped unit: what compile_query refuses on it is applied to its dense columns below
         row_unit = isinstance(q, QueryUnit) and is_row_unit(q)

@@ -223,8 +223,11 @@ class JoinSpec:
     """Equi-join of the outer table with `inner_table` on outer_key == inner_col.  Both sides may be
     lists of equal length (composite key -> keyed/"baseline" hash table, BaselineJoinHashTable); the
     table kind (one-to-one / one-to-many, perfect / keyed) is chosen from the inner table's data the
-    way PerfectJoinHashTable::reify / HashJoin::getInstance do (QE/JoinHashTable/HashJoin.cpp:258-330)."""
-    inner_table: str
+    way PerfectJoinHashTable::reify / HashJoin::getInstance do (QE/JoinHashTable/HashJoin.cpp:258-330).
+    `inner_table` names a table of the storage -- a result registered with joinable=True (Executor.register_columns) included, whose key
+    multiplicity Executor.compile measures on the device -- or is itself a QueryUnit, a join against a subquery, which
+    Executor.execute runs first and joins where it lies (Executor.compile refuses such a unit)."""
+    inner_table: Union[str, "QueryUnit"]
     outer_key: Union[Expr, Sequence[Expr]]
     inner_col: Union[str, Sequence[str]]
     type: str = "inner"  # inner | left | semi | anti  (JoinType, Shared/sqldefs.h:33)
@@ -302,8 +305,9 @@ class ResultSetOp:
 @dataclass
 class QueryUnit:
     """What one execution step needs (cf. RelAlgExecutionUnit).  `table` names a table of the storage, or is itself a
-    QueryUnit -- a FROM-subquery, which Executor.execute runs first and scans where it lies, in device memory (a registered
-    result can only be the outer table; Executor.compile refuses such a unit: its plan needs the inner result's statistics)."""
+    QueryUnit -- a FROM-subquery, which Executor.execute runs first and scans where it lies, in device memory; a
+    JoinSpec's inner_table may be one too (Executor.compile refuses either unit: its plan needs the inner result's
+    statistics).  A registered result is the outer table, and one registered as joinable also the inner table of a join."""
     table: Union[str, "QueryUnit"]
     quals: List[Cond] = field(default_factory=list)  # conjunction of conditions (each a Cmp or an And / Or / Not tree)
     joins: List[JoinSpec] = field(default_factory=list)

@@ -1032,6 +1032,8 @@ def _inner_keys_unique(inner: Table, cols: List[str], nulls_match: bool = False,
     answers from the data so that the plan names the table kind up front.  For a perfect table (one key column) the slots
     are worked out exactly as the fill does (fill_hash_join_buff_impl, HashJoinRuntime.cpp:197-240): decoded element,
     NULL rows dropped -- or, for a kBwEq join, filed under max + 1 --, slot = (elem - min) / bucket."""
+    if isinstance(inner, DeviceTable):
+        return _inner_max_matches(inner, cols, nulls_match, bucket) <= 1
     cache = inner.__dict__.setdefault("_unique_keys_cache", {})
     key = tuple(cols) + (bool(nulls_match), int(bucket))
     if key not in cache:
@@ -1060,9 +1062,64 @@ def _inner_keys_unique(inner: Table, cols: List[str], nulls_match: bool = False,
     return cache[key] <= 1
 
 
+def multiplicity_key(cols, nulls_match: bool = False, bucket: int = 1) -> tuple:
+    """The key of DeviceTable.key_multiplicity: what _inner_keys_unique is asked with."""
+    return (tuple(cols), bool(nulls_match), int(bucket))
+
+
 def _inner_max_matches(inner: Table, cols: List[str], nulls_match: bool = False, bucket: int = 1) -> int:
+    if isinstance(inner, DeviceTable):
+        # its rows were never on the host: the number was measured on the device (hdk_hip_key_multiplicity,
+        # Executor.compile) -- or it was not, and compile_query has no device to ask
+        rec = inner.key_multiplicity.get(multiplicity_key(cols, nulls_match, bucket))
+        if rec is None:
+            raise QueryMustRunOnCpu("a registered result can only be scanned as the outer table")
+        return int(rec[0]) or 1  # (no row filed: 1, as for a host table without a non-NULL key)
     _inner_keys_unique(inner, cols, nulls_match, bucket)
     return inner.__dict__["_unique_keys_cache"][tuple(cols) + (bool(nulls_match), int(bucket))]
+
+
+@dataclass
+class JoinKeyShape:
+    """How a join files the rows of its inner table, decided from the key columns' statistics alone: the arguments
+    _inner_keys_unique / _inner_max_matches are asked with (`cols`, `nulls_match`, `bucket`; the key of
+    DeviceTable.key_multiplicity is multiplicity_key of them), and the table they are filed in -- keyed, or perfect with
+    `entry_count` normalised slots of `bucket` values over [min_key, max_key] (+ 1 slot for the NULLs of a kBwEq join)."""
+    cols: List[str]
+    nulls_match: bool
+    bucket: int
+    keyed: bool
+    entry_count: int  # perfect: getNormalizedHashEntryCount; keyed: 0
+    hash_entry_count: int
+    key_bucket: int  # the day bucket of a DATE key, else 1: bucket_normalization of a perfect table
+    is_date: bool
+    bw_eq: bool
+    min_key: int
+    max_key: int
+
+    @property
+    def multiplicity_key(self) -> tuple:
+        return multiplicity_key(self.cols, self.nulls_match, self.bucket)
+
+
+def join_key_shape(inner: Table, j) -> Optional[JoinKeyShape]:
+    """The JoinKeyShape of JoinSpec `j` over `inner`; None when the first key column holds no value (an empty inner table)."""
+    icols = j.inner_cols
+    icol = inner.columns[icols[0]]
+    st = icol.table_stats()
+    if st.min is None:
+        return None
+    bw_eq = bool(j.null_safe)
+    # a DATE key is bucketized by day: bucket_normalization = the range's bucket (get_bucketized_hash_entry_info,
+    # QE/JoinHashTable/PerfectJoinHashTable.cpp:45-85; the bucket comes from getLeafColumnRange)
+    is_date = icol.type.kind == "date"
+    bucket = 86400 if is_date else 1
+    # HashEntryInfo: hash_entry_count = max - min + 1 (+ 1 slot for the NULLs of a kBwEq join), normalised by the bucket
+    hash_entry_count = int(st.max) - int(st.min) + 1 + (1 if bw_eq else 0)
+    range_entries = -(-hash_entry_count // bucket)  # getNormalizedHashEntryCount (HashJoinRuntime.h:46-55)
+    keyed = len(icols) > 1 or range_entries > 2**31 - 1  # TooManyHashEntries -> keyed table
+    return JoinKeyShape(list(icols), bw_eq and not keyed, 1 if keyed else bucket, keyed, 0 if keyed else range_entries,
+                        hash_entry_count, bucket, is_date, bw_eq, int(st.min), int(st.max))
 
 
 def _compile_joins_and_quals(b: "_Binder", q: QueryUnit, p: A.Plan):
@@ -1072,8 +1129,8 @@ def _compile_joins_and_quals(b: "_Binder", q: QueryUnit, p: A.Plan):
     p.num_joins = len(q.joins)
     for ji, j in enumerate(q.joins):
         inner = b.inner[ji]
-        if isinstance(inner, DeviceTable):
-            # (the one-to-one / matching-set decision, _inner_keys_unique, reads host fragments)
+        if isinstance(inner, DeviceTable) and not inner.joinable:
+            # (registered as every result was before joins reached them: the outer table only)
             raise QueryMustRunOnCpu("a registered result can only be scanned as the outer table")
         okeys, icols = j.outer_keys, j.inner_cols
         if len(okeys) != len(icols) or not 1 <= len(okeys) <= A.MAX_JOIN_KEYS:
@@ -1100,13 +1157,10 @@ def _compile_joins_and_quals(b: "_Binder", q: QueryUnit, p: A.Plan):
         if okt.is_fp:
             raise QueryMustRunOnCpu("join keys must be integers")
         jn.null_val = A.to_i64(okt.null_as_int64_or_double_bits())
-        bw_eq = bool(j.null_safe)
-        # a DATE key is bucketized by day: bucket_normalization = the range's bucket (get_bucketized_hash_entry_info,
-        # QE/JoinHashTable/PerfectJoinHashTable.cpp:45-85; the bucket comes from getLeafColumnRange)
-        is_date = icol.type.kind == "date"
+        shape = join_key_shape(inner, j)  # (what the executor measures a registered inner table by)
+        bw_eq, is_date, bucket = shape.bw_eq, shape.is_date, shape.key_bucket
         if is_date != (okt.kind == "date"):
             raise QueryMustRunOnCpu("a DATE join key needs a DATE on both sides")
-        bucket = 86400 if is_date else 1
         # key_col nullable or kBwEq: the probe gets the NULL (getHashJoinArgs, PerfectJoinHashTable.cpp:798-801) and is the
         # _bitwise form for kBwEq, else _nullable for a nullable key (codegenSlot, :1018-1031)
         jn.null_mode = A.JOIN_NULL_BITWISE if bw_eq else (A.JOIN_NULL_NULLABLE if okt.nullable else A.JOIN_NULL_NONE)
@@ -1114,11 +1168,9 @@ def _compile_joins_and_quals(b: "_Binder", q: QueryUnit, p: A.Plan):
         jn.type = {"inner": A.JOIN_INNER, "left": A.JOIN_LEFT, "semi": A.JOIN_SEMI, "anti": A.JOIN_ANTI}[j.type]
         semi = j.type in ("semi", "anti")  # for_semi_anti_join: the fill lets the first row of a key win
         jn.table_idx = ji
-        # HashEntryInfo: hash_entry_count = max - min + 1 (+ 1 slot for the NULLs of a kBwEq join), normalised by the bucket
-        hash_entry_count = int(st.max) - int(st.min) + 1 + (1 if bw_eq else 0)
-        range_entries = -(-hash_entry_count // bucket)  # getNormalizedHashEntryCount (HashJoinRuntime.h:46-55)
-        keyed = len(okeys) > 1 or range_entries > 2**31 - 1  # TooManyHashEntries -> keyed table
-        unique = semi or _inner_keys_unique(inner, icols, bw_eq and not keyed, 1 if keyed else bucket)
+        hash_entry_count, keyed = shape.hash_entry_count, shape.keyed
+        range_entries = -(-hash_entry_count // bucket)
+        unique = semi or _inner_keys_unique(inner, icols, shape.nulls_match, shape.bucket)
         if keyed:
             if bw_eq or is_date:
                 raise QueryMustRunOnCpu("null-safe / DATE keys on a keyed join table are outside the fixed kernel library")
@@ -1166,7 +1218,7 @@ def _compile_joins_and_quals(b: "_Binder", q: QueryUnit, p: A.Plan):
                            "hash_entry_count": hash_entry_count, "bucket": bucket, "bucketized": bool(is_date),
                            "uses_bw_eq": 1 if bw_eq else 0, "translated_null_build": int(st.max) + 1,
                            "for_semi_join": 1 if semi else 0,
-                           "max_matches": 1 if semi else _inner_max_matches(inner, icols, bw_eq and not keyed, 1 if keyed else bucket)})
+                           "max_matches": 1 if semi else _inner_max_matches(inner, icols, shape.nulls_match, shape.bucket)})
     # filter: a plain conjunction of comparisons keeps the per-conjunct staging; anything with OR / NOT becomes a
     # postfix program over the comparisons (hdk_hip_plan::filter_ops), evaluated at one stage
     leaves: List[Cmp] = []

@@ -66,13 +66,19 @@ class DeviceTable(Table):
     columns (hdk_hip_chunk_columns).  Column j of the block starts at block + j * out_capacity * 8 and is contiguous;
     fragment f of it starts fragment_rows * f rows further on, on a 256-byte boundary.  Every column is 8 bytes wide;
     `Column.fragments` are empty and `Column.stats` come from the device.  Owns the block until free(): the executor's
-    buffer cache hands out views of it and never stores or frees them.  It can only be the OUTER table of a unit: the
-    planner's one-to-one decision for an inner table reads host fragments."""
+    buffer cache hands out views of it and never stores or frees them.  It may be the outer table of a unit and, when it was
+    registered as `joinable` (register_columns(..., joinable=True); a table registered without stays the outer table only,
+    as every registered table was before), the INNER table of a join: what the planner reads from a host table's fragments for an inner table -- the largest matching set
+    of the join key -- is kept in `key_multiplicity`: {(tuple(key columns), nulls_match, bucket): (max_matches, occupied)},
+    the key plan.multiplicity_key builds, measured on the device (hdk_hip_key_multiplicity) by Executor.compile the first
+    time a join asks.  plan.compile_query alone has no device to ask and refuses a join whose number is missing."""
 
     def __init__(self, name, columns: List[Column], frag_rows: List[int], block, out_capacity: int, fragment_rows: int,
-                 device_id: int = 0):
+                 device_id: int = 0, joinable: bool = False):
         super().__init__(name, columns, frag_rows)
         self.block, self.out_capacity, self.fragment_rows, self.device_id = block, int(out_capacity), int(fragment_rows), device_id
+        self.joinable = bool(joinable)
+        self.key_multiplicity: Dict[tuple, tuple] = {}
 
     def _base(self) -> int:
         if self.block is None or not self.block.ptr:

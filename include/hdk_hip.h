@@ -1227,6 +1227,72 @@ int32_t hdk_hip_chunk_columns(const int64_t* cols, uint64_t capacity, int32_t nu
                               int32_t device_id, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The key multiplicity of a join key over dense columns: what the planner must know of an INNER table that lies in HBM.
+ * The reference finds out whether a one-to-one table will do by trying the fill (fill_one_to_one_hashtable returns -1 ->
+ * NeedsOneToManyHash, Builders/PerfectHashTableBuilder.h:134-141) and sizes a projection from the table it then has; here the
+ * plan names the table kind up front, so the largest matching set is measured first.  The call files every row exactly as the
+ * builds of this library will and leaves one record: max_matches -- the most rows filed under one key --, occupied -- the keys
+ * that hold a row --, rows_filed and rows_out_of_range.
+ *
+ * Input: `num_cols` dense columns of `num_rows` 8-byte words, column t at cols + t * capacity -- the block of a table made by
+ * hdk_hip_chunk_columns, or what any *_columns call writes.  `keys`: 1..HDK_HIP_MAX_JOIN_KEYS descriptors.  A word of a
+ * nullable key column that EQUALS null_bits (a bit compare) is NULL; a word of a column that is not nullable never is.
+ * Perfect route (num_keys == 1, entry_count > 0: the normalised slot count of the perfect table, `bucket` its
+ * bucket_normalization), a restatement of fill_hash_join_buff_impl (HashJoinRuntime.cpp:197-240): a NULL word is dropped, or
+ * with HDK_HIP_KEYS_NULLS_MATCH (the kBwEq build) filed under translated_null (= max + 1); a non-NULL word outside
+ * [min_val, max_val], or a word whose slot (word - min_val) / bucket is not below entry_count, counts in rows_out_of_range
+ * and is not filed -- the builds answer -2 there (stale statistics).  max_matches is the largest number of rows in one slot,
+ * occupied the number of slots that hold a row.  Method: a histogram of entry_count 32-bit counters in the workspace (the
+ * size of the one-to-one table the caller allocates anyway, with the same 2^31 - 1 limit), zeroed on the stream; one
+ * streaming pass over tiles of 4 096 rows with one non-returning atomic add per filed row, or ONE add of the lane count for
+ * 64 rows whose filing lanes all name the same slot (a column of one key, the long equal runs of a result that arrives
+ * sorted); a pass that reduces the histogram to one partial per block; a fold.  No atomics on the record.  ASYNCHRONOUS on
+ * `stream`: the host never waits; the record is complete when `stream` has drained.
+ * Sorted route (entry_count == 0: composite keys, and a single key whose range exceeds 2^31 - 1 slots -- the plans that take
+ * a keyed table): a row with a NULL in any component is skipped, as hdk_hip_fill_baseline_hash_join_buff skips it; rows match
+ * when every component word is equal; min_val / max_val / translated_null / bucket / the flag are not read.  The key columns
+ * are sorted by hdk_hip_sort_columns into a temporary that holds EVERY column up to the highest key column (that call copies
+ * whole blocks), and a longest-run pass over the sorted keys leaves one summary per tile of 4 096 rows -- (leading open run,
+ * trailing open run, best closed run, all-one-run flag, runs closed) --, folded with the associative combine.  A run whose
+ * rows carry a NULL component has weight 0.  occupied is the number of runs of weight > 0, rows_out_of_range is 0.
+ * This route SYNCHRONISES `stream` where hdk_hip_sort_columns does (once per key); the run pass and the fold are asynchronous.
+ * `workspace`: hdk_hip_key_multiplicity_workspace_bytes(num_rows, keys, num_keys, entry_count) bytes of device memory, 8-byte
+ * aligned (host arithmetic only; perfect: entry_count * 4 rounded up to 256 plus 64 KiB of partials; sorted: the temporary of
+ * (highest key column + 1) columns of num_rows rounded up to 32 words, the sort's own workspace and 32 bytes per tile; 0 for
+ * num_rows == 0 or arguments the call would refuse), or NULL -- the library then takes it from the stream's memory pool.
+ * Errors, all found before any device is touched (HDK_HIP_ERR_INVALID_ARG with a message): a NULL keys / result (cols with
+ * rows), num_keys outside 1..3, a key column outside [0, num_cols), num_rows >= 2^32, num_rows > capacity, entry_count < 0 or
+ * > 2^31 - 1, entry_count > 0 with more than one key, bucket < 1, unknown flags, a workspace that is too small or not 8-byte
+ * aligned, result not 8-byte aligned, any two of cols, result and workspace overlapping.
+ * num_rows == 0: an all-zero record is stored on the stream, nothing is launched.  The input is never modified.
+ * ---------------------------------------------------------------------------------------- */
+#define HDK_HIP_KEYS_NULLS_MATCH 1u /* flags: NULL keys are filed under translated_null (the kBwEq build) */
+
+typedef struct hdk_hip_multiplicity_key {
+  int32_t col;             /* column of the input block */
+  uint8_t nullable;        /* 0: null_bits is an ordinary value */
+  uint8_t pad_[3];
+  int64_t null_bits;       /* the column's in-band NULL */
+  int64_t min_val;         /* perfect route: the range the table was sized from (JoinColumnTypeInfo) */
+  int64_t max_val;
+  int64_t translated_null; /* perfect route with HDK_HIP_KEYS_NULLS_MATCH: max_val + 1 */
+} hdk_hip_multiplicity_key;
+
+typedef struct hdk_hip_key_multiplicity_result {
+  uint64_t max_matches;
+  uint64_t occupied;
+  uint64_t rows_filed;
+  uint64_t rows_out_of_range;
+} hdk_hip_key_multiplicity_result;
+
+size_t hdk_hip_key_multiplicity_workspace_bytes(uint64_t num_rows, const hdk_hip_multiplicity_key* keys, int32_t num_keys,
+                                                int64_t entry_count);
+int32_t hdk_hip_key_multiplicity(const int64_t* cols, uint64_t capacity, int32_t num_cols, uint64_t num_rows,
+                                 const hdk_hip_multiplicity_key* keys, int32_t num_keys, int64_t entry_count, int64_t bucket,
+                                 uint32_t flags, hdk_hip_key_multiplicity_result* result, void* workspace, size_t workspace_bytes,
+                                 int32_t device_id, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Environment switches (MI355X addition; no reference counterpart: the reference's knobs are Config fields,
  * Shared/Config.h).  libhdk_hip.so reads its HDK_HIP_* variables (tests and A/B measurements, none needed
  * in production) ONCE per process, at the first launch that asks for one -- never per launch, so a host that calls
